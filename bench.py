@@ -13,6 +13,14 @@ the implicit envelope to beat is its fixed per-claim overhead (≥1 s
 post-patch sleep on the provision path + 5 s termination polls).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--concurrent C]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line; nothing else is measured. On a host with a GPU, setup asks the native
+node agent which device that is (discovery only, no kernel launch) and names
+it in the result's config block. --dump-outputs DIR additionally writes what
+the last timed step produced (see dump_outputs) as DIR/<name>.npy so two
+builds can be compared output for output. --full is reserved for
+measurements beyond the headline figure (there are none today).
 For N>1 the driver launches this under torch.distributed.run, one rank per
 GPU; the workload is controller plumbing (CPU-bound), ranks run independent
 provisioner stacks and aggregate via gloo (weak scaling).
@@ -58,22 +66,128 @@ def build_harness(create_latency: float = 0.0, ready_latency: float = 0.0) -> Ha
     )
 
 
-async def one_step(h: Harness, step: int, concurrent: int, latencies: list) -> None:
+async def one_step(h: Harness, step: int, concurrent: int, latencies: list) -> dict:
+    """One churn cycle. Returns what a caller of the cycle receives: the
+    Initialized NodeClaims (in name order) and, per claim, whether its
+    deletion was observed to completion."""
     names = [f"s{step % 1000:03d}c{i:02d}" for i in range(concurrent)]
 
-    async def provision(name: str) -> None:
+    async def provision(name: str) -> dict:
         t0 = time.monotonic()
         await h.kube.create(h.make_nodeclaim(name, VM_SIZE))
-        await h.wait_initialized(name, timeout=60.0, interval=0.001)
+        nc = await h.wait_initialized(name, timeout=60.0, interval=0.001)
         latencies.append(time.monotonic() - t0)
+        return nc
 
-    await asyncio.gather(*(provision(n) for n in names))
+    claims = await asyncio.gather(*(provision(n) for n in names))
 
-    async def teardown(name: str) -> None:
+    async def teardown(name: str) -> bool:
         await h.kube.delete(karpv1.API_VERSION, karpv1.KIND_NODECLAIM, name)
-        await h.wait_gone(karpv1.API_VERSION, karpv1.KIND_NODECLAIM, name, timeout=60.0, interval=0.001)
+        return bool(
+            await h.wait_gone(karpv1.API_VERSION, karpv1.KIND_NODECLAIM, name, timeout=60.0, interval=0.001)
+        )
 
-    await asyncio.gather(*(teardown(n) for n in names))
+    gone = await asyncio.gather(*(teardown(n) for n in names))
+    return {"claims": list(claims), "gone": list(gone)}
+
+
+RESOURCE_NAMES = ("cpu", "memory", "ephemeral-storage", "pods", karpv1.AMD_GPU_RESOURCE)
+CONDITION_TYPES = ("Launched", "Registered", "Initialized", "Ready")
+_QUANTITY_SUFFIXES = {
+    "Ki": 2.0**10, "Mi": 2.0**20, "Gi": 2.0**30, "Ti": 2.0**40, "Pi": 2.0**50, "Ei": 2.0**60,
+    "m": 1e-3, "k": 1e3, "M": 1e6, "G": 1e9, "T": 1e12, "P": 1e15, "E": 1e18,
+}
+
+
+def quantity_to_float(q) -> float:
+    """Kubernetes resource quantity ("128", "2036Gi", "500m") as a float;
+    NaN when absent."""
+    if q is None:
+        return float("nan")
+    q = str(q)
+    for suffix in sorted(_QUANTITY_SUFFIXES, key=len, reverse=True):
+        if q.endswith(suffix):
+            return float(q[: -len(suffix)]) * _QUANTITY_SUFFIXES[suffix]
+    return float(q)
+
+
+MAX_DUMP_BYTES = 64 * 1000 * 1000
+# float64 columns per claim: 5 + 5 resources, 4 conditions, 5 identity, 2 labels, 1 gone
+DUMP_BYTES_PER_CLAIM = 8 * (2 * len(RESOURCE_NAMES) + len(CONDITION_TYPES) + 5 + 2 + 1)
+
+
+def dump_outputs(out_dir: str, last: dict) -> None:
+    """Write the last timed step's results as float64 .npy arrays, one row
+    per NodeClaim in name order. Only run-invariant fields are kept (no
+    UIDs, timestamps or resourceVersions), so equal arguments give equal
+    files (MAX_DUMP_BYTES in all; a step with more claims than fit is cut
+    to a fixed, seeded sample of its rows, kept in name order):
+
+      capacity.npy / allocatable.npy  [claims, 5]  status quantities, columns
+                                      RESOURCE_NAMES (bytes for memory/storage)
+      conditions.npy                  [claims, 4]  CONDITION_TYPES; 1 True,
+                                      0 otherwise, -1 condition absent
+      identity.npy                    [claims, 5]  CRC-32 of name, nodeName,
+                                      providerID, instance-type and
+                                      capacity-type labels
+      labels.npy                      [claims, 2]  amd.com/gpu.count label,
+                                      number of labels carrying the amd.com/ prefix
+      gone.npy                        [claims]     1 if deletion completed
+    """
+    import zlib
+
+    import numpy as np
+
+    claims, gone = last["claims"], last["gone"]
+    # six files, each with a 128-byte .npy header
+    keep = (MAX_DUMP_BYTES - 6 * 128) // DUMP_BYTES_PER_CLAIM
+    if len(claims) > keep:
+        rows = sorted(np.random.default_rng(0).choice(len(claims), size=keep, replace=False))
+        claims, gone = [claims[i] for i in rows], [gone[i] for i in rows]
+
+    def crc(text) -> float:
+        return float(zlib.crc32(str(text or "").encode()))
+
+    def resources(nc: dict, field: str):
+        quantities = nc.get("status", {}).get(field, {})
+        return [quantity_to_float(quantities.get(r)) for r in RESOURCE_NAMES]
+
+    def conditions(nc: dict):
+        by_type = {c.get("type"): c.get("status") for c in nc.get("status", {}).get("conditions", [])}
+        return [
+            -1.0 if t not in by_type else (1.0 if by_type[t] == "True" else 0.0)
+            for t in CONDITION_TYPES
+        ]
+
+    def identity(nc: dict):
+        labels = nc["metadata"].get("labels", {})
+        status = nc.get("status", {})
+        return [
+            crc(nc["metadata"]["name"]),
+            crc(status.get("nodeName")),
+            crc(status.get("providerID")),
+            crc(labels.get(karpv1.INSTANCE_TYPE_LABEL_KEY)),
+            crc(labels.get("karpenter.sh/capacity-type")),
+        ]
+
+    def label_facts(nc: dict):
+        labels = nc["metadata"].get("labels", {})
+        return [
+            quantity_to_float(labels.get("amd.com/gpu.count")),
+            float(sum(1 for k in labels if k.startswith("amd.com/"))),
+        ]
+
+    arrays = {
+        "capacity": [resources(nc, "capacity") for nc in claims],
+        "allocatable": [resources(nc, "allocatable") for nc in claims],
+        "conditions": [conditions(nc) for nc in claims],
+        "identity": [identity(nc) for nc in claims],
+        "labels": [label_facts(nc) for nc in claims],
+        "gone": [1.0 if g else 0.0 for g in gone],
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, rows in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(rows, dtype=np.float64))
 
 
 async def run_bench(
@@ -101,15 +215,37 @@ async def run_bench(
         for s in range(warmup):
             await one_step(h, s, concurrent, warm_lat)
         latencies: list = []
+        last: dict = {"claims": [], "gone": []}
         t0 = time.monotonic()
         for s in range(warmup, warmup + steps):
             sample_rss(s)
-            await one_step(h, s, concurrent, latencies)
+            last = await one_step(h, s, concurrent, latencies)
         sample_rss(warmup + steps)
         elapsed = time.monotonic() - t0
-        return {"elapsed_s": elapsed, "latencies": latencies, "rss": rss}
+        return {"elapsed_s": elapsed, "latencies": latencies, "rss": rss, "last": last}
     finally:
         await h.stop()
+
+
+def identify_device(gpu_present: bool, rank: int = 0):
+    """Which device a figure was measured next to, as the native node agent
+    (the gfx950 HIP library) discovers it: index, name, arch, HBM size and
+    CU count. Discovery only, no kernel is launched. A host without a GPU
+    has no device and the library is not touched. The figure does not depend
+    on the answer, so a missing library or a failed query does not stop the
+    run: it is reported on stderr and recorded as {"error": ...}."""
+    if not gpu_present:
+        return None
+    from gpu_provisioner_amd.nodeagent import NodeAgent, NodeAgentError
+
+    try:
+        agent = NodeAgent()
+        dev = rank % agent.device_count()
+        name, arch, hbm, cus = agent.device_info(dev)
+    except NodeAgentError as e:
+        print(f"bench: device not identified: {e}", file=sys.stderr)
+        return {"error": str(e)}
+    return {"index": dev, "name": name, "arch": arch, "hbm_gb": round(hbm / 1e9, 1), "cus": cus}
 
 
 def main() -> None:
@@ -127,6 +263,11 @@ def main() -> None:
                     help="write per-step RSS samples (soak memory evidence) to this JSON file")
     ap.add_argument("--rss-every", type=int, default=100,
                     help="sample RSS every N steps when --rss-out is set")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure "
+                         "(none exist today; a plain run is already minimal)")
     args = ap.parse_args()
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -152,6 +293,7 @@ def main() -> None:
             torch.cuda.synchronize()
 
     sync()
+    device = identify_device(cuda, rank)
     result = asyncio.run(
         run_bench(
             args.steps, args.warmup, args.concurrent,
@@ -172,6 +314,10 @@ def main() -> None:
         }
         with open(args.rss_out, "w") as f:
             json.dump(summary, f, indent=1)
+
+    if args.dump_outputs and rank == 0:
+        # rank 0's own stack; every rank runs the same deterministic workload
+        dump_outputs(args.dump_outputs, result["last"])
 
     elapsed = result["elapsed_s"]
     if dist is not None:
@@ -221,6 +367,8 @@ def main() -> None:
                         "model": "MI355X NodeClaim provisioning (karpenter CloudProvider contract)",
                         "vm_sku": VM_SIZE,
                         "concurrent_nodeclaims": args.concurrent,
+                        # rank 0's device as seen by the native node agent
+                        "device": device,
                         "cloud": (
                             "in-memory fake AKS, zero latency (BASELINE config #1)"
                             if not (args.create_latency or args.ready_latency)

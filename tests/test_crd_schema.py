@@ -5,7 +5,6 @@ enough to catch drift between the Python surface and the CRD the chart
 installs."""
 import os
 
-import pytest
 import yaml
 
 from gpu_provisioner_amd.apis import v1 as karpv1
@@ -113,31 +112,11 @@ def test_validator_rejects_malformed():
 # ------------------------------------------------- reference parity (r02)
 
 
-def test_crd_parity_with_reference():
-    """Field-by-field structural diff against the reference chart's CRD
-    (hack/crd_parity.py). Runs wherever the reference tree
-    is available; deliberate deltas must be documented in the script."""
-    import importlib.util
-
-    ref = "/root/reference/charts/gpu-provisioner/crds/karpenter.sh_nodeclaims.yaml"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not available")
-    spec = importlib.util.spec_from_file_location(
-        "crd_parity", os.path.join(ROOT, "hack", "crd_parity.py")
-    )
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    result = mod.compare(ref, CRD_PATH)
-    assert not result["missing"], f"reference features missing: {result['missing']}"
-    assert not result["different"], f"feature values differ: {result['different']}"
-    assert not result["columns_missing"], result["columns_missing"]
-    assert result["subresources_ok"]
-
-
 def test_crd_feature_manifest():
     """Key validation features asserted WITHOUT the reference tree (CI
     guard): extracted facts from the karpenter.sh/v1 schema that must not
-    regress."""
+    regress. The full field-by-field diff against the reference chart's CRD
+    is the manual tool hack/crd_parity.py (report: CRD_PARITY.md)."""
     schema = load_schema()
     spec = schema["properties"]["spec"]
     assert sorted(spec["required"]) == ["nodeClassRef", "requirements"]
