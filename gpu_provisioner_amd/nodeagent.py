@@ -5,7 +5,8 @@ node is trusted, and feeds the node.health repair policy with on-node
 evidence. Fails LOUDLY if the native library is missing on a GPU machine —
 there is no eager/python fallback for the hardware checks.
 
-CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]``
+CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
+[--memtest-bytes N]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -34,9 +35,60 @@ MIN_XGMI_BW_GBS = 30.0
 # measured ~4.9 TB/s on healthy silicon (profiles/), floor leaves margin
 MIN_SDMA_BW_GBS = 3000.0
 
+# C ABI return codes (nodeagent/agent.hip)
+NA_OK = 0
+NA_ERR_HIP = -1
+NA_ERR_VERIFY = -2
+NA_ERR_ARG = -3
+
+# HBM data-integrity test. Seed 0 would make vector 0 all-zeros/all-ones, so
+# the default is non-zero ("MI355XMT"); round r uses seed + r.
+DEFAULT_MEMTEST_SEED = 0x4D493335_35584D54
+NO_BAD_OFFSET = (1 << 64) - 1
+# the agent never asks for more than this share of what the device reports
+# free: the node may be running workloads
+MEMTEST_FREE_FRACTION_PCT = 90
+
 
 class NodeAgentError(RuntimeError):
     pass
+
+
+class MemtestAllocError(NodeAgentError):
+    """The memtest region could not be allocated (busy GPU) — not a fault."""
+
+
+class _MemtestResultC(ctypes.Structure):
+    _fields_ = [
+        ("bytes_tested", ctypes.c_uint64),
+        ("bad_words", ctypes.c_uint64),
+        ("first_bad_offset", ctypes.c_uint64),
+        ("xor_mask", ctypes.c_uint64),
+    ]
+
+
+@dataclass
+class MemtestResult:
+    """Outcome of a pattern verify. ``bad_words`` counts 64-bit words,
+    ``first_bad_offset`` is a byte offset from the region start
+    (``NO_BAD_OFFSET`` = none), ``xor_mask`` the OR of got^want over all bad
+    words (the failing data bits)."""
+
+    bytes_tested: int = 0
+    bad_words: int = 0
+    first_bad_offset: int = NO_BAD_OFFSET
+    xor_mask: int = 0
+    gbs: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.bad_words == 0
+
+    def describe(self) -> str:
+        return (
+            f"{self.bad_words} bad 64-bit words in {self.bytes_tested} bytes, "
+            f"first at offset {self.first_bad_offset:#x}, failing bits {self.xor_mask:#x}"
+        )
 
 
 def _load_lib() -> ctypes.CDLL:
@@ -66,6 +118,11 @@ class GPUReport:
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
+    # HBM data-integrity test (opt-in; all "not run" by default)
+    hbm_memtest_bytes: int = 0
+    hbm_memtest_bad_words: int = 0
+    hbm_memtest_gbs: float = 0.0
+    hbm_memtest_skipped: str = ""  # reason, when requested but not run
 
 
 @dataclass
@@ -171,6 +228,89 @@ class NodeAgent:
             raise NodeAgentError(f"sdma_bandwidth({dev}): {self._err()}")
         return out.value
 
+    # -- HBM data integrity --------------------------------------------------
+
+    def mem_info(self, dev: int) -> tuple:
+        """(free_bytes, total_bytes) of device memory right now."""
+        free = ctypes.c_longlong(0)
+        total = ctypes.c_longlong(0)
+        if self.lib.na_mem_info(dev, ctypes.byref(free), ctypes.byref(total)) != NA_OK:
+            raise NodeAgentError(f"mem_info({dev}): {self._err()}")
+        return free.value, total.value
+
+    def memtest_fill(self, dev: int, ptr: int, bytes_: int,
+                     seed: int = DEFAULT_MEMTEST_SEED, invert: bool = False) -> int:
+        """Write the test pattern to caller-owned device memory (``ptr``
+        16-byte aligned, ``bytes_`` a positive multiple of 16). Returns the
+        C return code (``NA_ERR_ARG`` for a bad pointer/size)."""
+        return self.lib.na_memtest_fill(
+            dev, ctypes.c_void_p(ptr), ctypes.c_longlong(bytes_),
+            ctypes.c_ulonglong(seed), int(bool(invert)),
+        )
+
+    def memtest_verify(self, dev: int, ptr: int, bytes_: int,
+                       seed: int = DEFAULT_MEMTEST_SEED, invert: bool = False,
+                       flip: bool = False) -> tuple:
+        """Compare caller-owned device memory against the pattern; with
+        ``flip`` also store the complement of the EXPECTED pattern. Returns
+        ``(rc, MemtestResult)``; rc is ``NA_ERR_VERIFY`` on any mismatch."""
+        res = _MemtestResultC()
+        rc = self.lib.na_memtest_verify(
+            dev, ctypes.c_void_p(ptr), ctypes.c_longlong(bytes_),
+            ctypes.c_ulonglong(seed), int(bool(invert)), int(bool(flip)), ctypes.byref(res),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, MemtestResult()
+        return rc, MemtestResult(
+            res.bytes_tested, res.bad_words, res.first_bad_offset, res.xor_mask
+        )
+
+    def hbm_memtest(self, dev: int, bytes_: int, rounds: int = 1,
+                    seed: int = DEFAULT_MEMTEST_SEED) -> MemtestResult:
+        """Pattern-test ``bytes_`` of HBM the agent allocates itself (in
+        chunks): per round fill(seed+r) -> verify+invert -> verify, so every
+        cell is read back at both polarities; the pattern is a bijection of
+        the address, so aliased address lines mismatch too. Mismatches come
+        back in the result (``.ok`` False), not as an exception.
+
+        Any size from 16 bytes is allowed, but a region under 512 MiB is
+        served largely from the 256 MiB Infinity Cache rather than DRAM —
+        it still checks the data path, not the HBM cells. ECC-corrected
+        single-bit errors are invisible to this test by design."""
+        res = _MemtestResultC()
+        gbs = ctypes.c_double(0)
+        rc = self.lib.na_hbm_memtest(
+            dev, ctypes.c_longlong(bytes_), rounds, ctypes.c_ulonglong(seed),
+            ctypes.byref(res), ctypes.byref(gbs),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = MemtestAllocError if "allocation failed" in err else NodeAgentError
+            raise cls(f"hbm_memtest({dev}): {err}")
+        return MemtestResult(
+            res.bytes_tested, res.bad_words, res.first_bad_offset, res.xor_mask, gbs.value
+        )
+
+    def _run_memtest(self, g: GPUReport, memtest_bytes: int) -> None:
+        free, _total = self.mem_info(g.index)
+        want = min(memtest_bytes, free * MEMTEST_FREE_FRACTION_PCT // 100) & ~15
+        if want < 16:
+            g.hbm_memtest_skipped = (
+                f"only {free} bytes of device memory free; nothing left to test"
+            )
+            return
+        try:
+            res = self.hbm_memtest(g.index, want)
+        except MemtestAllocError as e:
+            # a busy GPU must not get its node replaced for lack of free memory
+            g.hbm_memtest_skipped = str(e)
+            return
+        g.hbm_memtest_bytes = res.bytes_tested
+        g.hbm_memtest_bad_words = res.bad_words
+        g.hbm_memtest_gbs = round(res.gbs, 1)
+        if not res.ok:
+            g.problems.append(f"HBM memtest: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         if self.lib.na_p2p_matrix(n, buf) != 0:
@@ -188,7 +328,14 @@ class NodeAgent:
 
     # -- full health check ---------------------------------------------------
 
-    def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30) -> NodeReport:
+    def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
+              memtest_bytes: int = 0) -> NodeReport:
+        """Full health battery. ``memtest_bytes`` > 0 additionally runs the
+        HBM data-integrity test on that many bytes per GPU, clamped to 90 %
+        of what the device reports free; if nothing can be allocated the
+        reason lands in ``hbm_memtest_skipped`` and the GPU stays healthy.
+        Regions under 512 MiB are allowed but are served largely from the
+        256 MiB Infinity Cache, not DRAM. 0 (default) runs nothing new."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -239,6 +386,8 @@ class NodeAgent:
                     g.problems.append(
                         f"SDMA D2D bandwidth {g.sdma_bw_gbs} GB/s below floor {MIN_SDMA_BW_GBS}"
                     )
+                if memtest_bytes > 0:
+                    self._run_memtest(g, memtest_bytes)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -326,6 +475,15 @@ def main(argv=None) -> int:
     ap.add_argument("--expect-gpus", type=int, default=0)
     ap.add_argument("--bw-bytes", type=int, default=1 << 30)
     ap.add_argument(
+        "--memtest-bytes",
+        type=int,
+        default=0,
+        metavar="N",
+        help="also pattern-test N bytes of HBM per GPU (fill / verify+invert / verify), "
+        "clamped to 90%% of free device memory; 0 = off. Regions under 512 MiB are "
+        "allowed but are served largely from the 256 MiB Infinity Cache, not DRAM",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -334,7 +492,11 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     try:
         agent = NodeAgent()
-        report = agent.check(expect_gpus=args.expect_gpus, bw_bytes=args.bw_bytes)
+        report = agent.check(
+            expect_gpus=args.expect_gpus,
+            bw_bytes=args.bw_bytes,
+            memtest_bytes=args.memtest_bytes,
+        )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))
         return 2

@@ -5,7 +5,8 @@
 // trusted (and as the node.health controller's on-node evidence), this agent
 // validates the GPU stack end to end: device discovery (gfx950 arch, 288 GB
 // HBM3E), an HBM bandwidth self-test (float4 streaming copy; healthy nodes
-// reach ~6 TB/s of the 8 TB/s peak), a VALU FMA correctness check, an MFMA
+// reach ~6 TB/s of the 8 TB/s peak), an opt-in HBM data-integrity test
+// (pattern fill / verify+invert / verify, memtest.h), a VALU FMA correctness check, an MFMA
 // matrix-pipe check (v_mfma_f32_16x16x4_f32 — the CDNA4 matrix core the ML
 // workloads will live on), and the xGMI peer-to-peer link matrix.
 //
@@ -18,10 +19,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
+
+#include "memtest.h"
 
 #define NA_OK 0
 #define NA_ERR_HIP -1
 #define NA_ERR_VERIFY -2
+#define NA_ERR_ARG -3
 
 #define HIP_CHECK(expr)                                                                  \
     do {                                                                                 \
@@ -748,4 +753,232 @@ extern "C" int na_p2p_bandwidth(int src, int dst, long long bytes, int iters, do
     (void)hipFree(dbuf);
     (void)hipSetDevice(src);
     return NA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// HBM data-integrity test (kernels in memtest.h)
+// ---------------------------------------------------------------------------
+//
+// The bandwidth probe above never looks at what arrived; this does. One
+// round is fill(seed+r) → verify+invert → verify(inverted): every cell is
+// read back at both polarities, and because the pattern is a bijection of
+// the vector index an aliased address line is a mismatch too. Phases are
+// separate launches over the whole region, so read-back never comes from a
+// register. HBM ECC silently corrects single-bit cell errors; what shows up
+// here is what ECC does not fix — uncorrected/multi-bit corruption,
+// addressing faults and data-path faults.
+
+typedef struct {
+    uint64_t bytes_tested, bad_words, first_bad_offset /* UINT64_MAX = none */, xor_mask;
+} na_memtest_result;
+
+extern "C" int na_mem_info(int dev, long long* free_bytes, long long* total_bytes) {
+    HIP_CHECK(hipSetDevice(dev));
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if (free_bytes) *free_bytes = (long long)free_b;
+    if (total_bytes) *total_bytes = (long long)total_b;
+    return NA_OK;
+}
+
+// One launch covers at most 1 GiB (16384 workgroups — the copy probe's
+// measured grid); larger regions take several launches. na_hbm_memtest
+// allocates in chunks of the same size.
+static const size_t MT_MAX_LAUNCH_VECS = (size_t)1 << 26;
+
+static int mt_launch(int mode, void* dptr, size_t nvec, mt_u64 v0, mt_u64 seed, int invert,
+                     mt_accum* d_acc) {
+    const mt_u64 base = seed * 0x9E3779B97F4A7C15ULL;
+    const mt_u64 inv = invert ? ~0ULL : 0ULL;
+    for (size_t off = 0; off < nvec; off += MT_MAX_LAUNCH_VECS) {
+        size_t n = nvec - off < MT_MAX_LAUNCH_VECS ? nvec - off : MT_MAX_LAUNCH_VECS;
+        mt_vec* p = reinterpret_cast<mt_vec*>(dptr) + off;
+        dim3 grid((unsigned)((n + MT_TILE - 1) / MT_TILE)), block(MT_BLOCK);
+        if (mode == MT_FILL)
+            memtest_kernel<MT_FILL><<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
+        else if (mode == MT_VERIFY)
+            memtest_kernel<MT_VERIFY><<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
+        else
+            memtest_kernel<MT_VERIFY_FLIP><<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
+        HIP_CHECK(hipGetLastError());
+    }
+    return NA_OK;
+}
+
+// Device-side accumulator, freed on every path.
+struct mt_dev_accum {
+    mt_accum* d = nullptr;
+    ~mt_dev_accum() {
+        if (d) (void)hipFree(d);
+    }
+    int init() {
+        HIP_CHECK(hipMalloc(&d, sizeof(mt_accum)));
+        mt_accum zero = {0, UINT64_MAX, 0};
+        HIP_CHECK(hipMemcpy(d, &zero, sizeof(zero), hipMemcpyHostToDevice));
+        return NA_OK;
+    }
+    int read(uint64_t bytes, na_memtest_result* out) {
+        mt_accum h;
+        HIP_CHECK(hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost));
+        out->bytes_tested = bytes;
+        out->bad_words = h.bad_words;
+        out->first_bad_offset = h.first_bad_offset;
+        out->xor_mask = h.xor_mask;
+        return NA_OK;
+    }
+};
+
+static int mt_check_args(const char* fn, const void* dptr, long long bytes) {
+    if (dptr == nullptr || ((uintptr_t)dptr & 15) != 0 || bytes <= 0 || (bytes & 15) != 0) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "%s: pointer %p must be 16-byte aligned and bytes (%lld) a positive "
+                      "multiple of 16",
+                      fn, dptr, bytes);
+        return NA_ERR_ARG;
+    }
+    return NA_OK;
+}
+
+static int mt_verdict(const na_memtest_result* r) {
+    if (r->bad_words == 0) return NA_OK;
+    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                  "hbm memtest: %llu bad 64-bit words in %llu bytes, first at offset 0x%llx, "
+                  "failing bits 0x%016llx",
+                  (unsigned long long)r->bad_words, (unsigned long long)r->bytes_tested,
+                  (unsigned long long)r->first_bad_offset, (unsigned long long)r->xor_mask);
+    return NA_ERR_VERIFY;
+}
+
+// Pointer-level calls on caller-owned device memory (16-byte aligned,
+// bytes a positive multiple of 16). Both synchronise before returning.
+extern "C" int na_memtest_fill(int dev, void* dptr, long long bytes, unsigned long long seed,
+                               int invert) {
+    int rc = mt_check_args("na_memtest_fill", dptr, bytes);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipSetDevice(dev));
+    rc = mt_launch(MT_FILL, dptr, (size_t)bytes / 16, 0, seed, invert, nullptr);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// flip != 0: also store the complement of the expected pattern (the region
+// then holds the pattern for !invert). Returns NA_ERR_VERIFY when any word
+// mismatched; *out is filled either way.
+extern "C" int na_memtest_verify(int dev, void* dptr, long long bytes, unsigned long long seed,
+                                 int invert, int flip, na_memtest_result* out) {
+    int rc = mt_check_args("na_memtest_verify", dptr, bytes);
+    if (rc != NA_OK) return rc;
+    if (out == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_memtest_verify: out must not be null");
+        return NA_ERR_ARG;
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    mt_dev_accum acc;
+    rc = acc.init();
+    if (rc != NA_OK) return rc;
+    rc = mt_launch(flip ? MT_VERIFY_FLIP : MT_VERIFY, dptr, (size_t)bytes / 16, 0, seed, invert,
+                   acc.d);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipDeviceSynchronize());
+    rc = acc.read((uint64_t)bytes, out);
+    if (rc != NA_OK) return rc;
+    return mt_verdict(out);
+}
+
+// Everything na_hbm_memtest owns; the destructor frees it on every path.
+struct mt_region {
+    std::vector<void*> chunks;
+    std::vector<size_t> chunk_vecs;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~mt_region() {
+        for (void* c : chunks) (void)hipFree(c);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// Whole test on a region the agent allocates itself, in chunks of at most
+// 1 GiB so no huge contiguous allocation is needed. pass_gbs (optional,
+// 3 doubles) receives GB/s of the fill, verify+invert and verify passes;
+// *gbs the aggregate over all passes (4x the region per round), HIP-event
+// timed. `bytes` is rounded down to a multiple of 16.
+extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
+                                     unsigned long long seed, na_memtest_result* out,
+                                     double* gbs, double* pass_gbs) {
+    bytes &= ~15LL;
+    if (bytes < 16 || rounds < 1 || out == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_hbm_memtest: need bytes >= 16 (got %lld), rounds >= 1 (got %d) and a "
+                      "result pointer",
+                      bytes, rounds);
+        return NA_ERR_ARG;
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t nvec = (size_t)bytes / 16;
+    mt_region reg;
+    for (size_t off = 0; off < nvec; off += MT_MAX_LAUNCH_VECS) {
+        size_t n = nvec - off < MT_MAX_LAUNCH_VECS ? nvec - off : MT_MAX_LAUNCH_VECS;
+        void* c = nullptr;
+        hipError_t e = hipMalloc(&c, n * 16);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // consumed here, not by a later check
+            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                          "hbm memtest: allocation failed after %zu of %lld bytes: %s", off * 16,
+                          bytes, hipGetErrorString(e));
+            return NA_ERR_HIP;
+        }
+        reg.chunks.push_back(c);
+        reg.chunk_vecs.push_back(n);
+    }
+    mt_dev_accum acc;
+    int rc = acc.init();
+    if (rc != NA_OK) return rc;
+    for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventCreate(&reg.ev[i]));
+
+    // each phase sweeps the WHOLE region before the next starts, so by the
+    // time a chunk is read back the rest of the region has gone through the
+    // caches in between
+    static const int phase_mode[3] = {MT_FILL, MT_VERIFY_FLIP, MT_VERIFY};
+    static const int phase_invert[3] = {0, 0, 1};
+    double phase_ms[3] = {0.0, 0.0, 0.0};
+    for (int r = 0; r < rounds; ++r) {
+        HIP_CHECK(hipEventRecord(reg.ev[0]));
+        for (int ph = 0; ph < 3; ++ph) {
+            size_t off = 0;
+            for (size_t c = 0; c < reg.chunks.size(); ++c) {
+                rc = mt_launch(phase_mode[ph], reg.chunks[c], reg.chunk_vecs[c], off,
+                               seed + (mt_u64)r, phase_invert[ph], acc.d);
+                if (rc != NA_OK) return rc;
+                off += reg.chunk_vecs[c];
+            }
+            HIP_CHECK(hipEventRecord(reg.ev[ph + 1]));
+        }
+        HIP_CHECK(hipEventSynchronize(reg.ev[3]));
+        for (int ph = 0; ph < 3; ++ph) {
+            float ms = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&ms, reg.ev[ph], reg.ev[ph + 1]));
+            phase_ms[ph] += ms;
+        }
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    rc = acc.read((uint64_t)bytes, out);
+    if (rc != NA_OK) return rc;
+    // bytes moved per round: fill writes 1x, verify+invert reads and writes
+    // (2x), verify reads 1x
+    static const double phase_traffic[3] = {1.0, 2.0, 1.0};
+    double total_ms = 0.0;
+    for (int ph = 0; ph < 3; ++ph) {
+        total_ms += phase_ms[ph];
+        if (pass_gbs)
+            pass_gbs[ph] = phase_traffic[ph] * (double)bytes * rounds / (phase_ms[ph] * 1e6);
+    }
+    if (gbs) *gbs = 4.0 * (double)bytes * rounds / (total_ms * 1e6);
+    return mt_verdict(out);
+}
+
+extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned long long seed,
+                              na_memtest_result* out, double* gbs) {
+    return na_hbm_memtest_passes(dev, bytes, rounds, seed, out, gbs, nullptr);
 }
