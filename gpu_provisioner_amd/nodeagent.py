@@ -6,7 +6,7 @@ evidence. Fails LOUDLY if the native library is missing on a GPU machine —
 there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
-[--memtest-bytes N]``
+[--memtest-bytes N] [--mfma-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -48,6 +48,20 @@ NO_BAD_OFFSET = (1 << 64) - 1
 # the agent never asks for more than this share of what the device reports
 # free: the node may be running workloads
 MEMTEST_FREE_FRACTION_PCT = 90
+
+# Chip-wide matrix-core sweep. The default seed is "MI355XMS"; dtype codes
+# are those of nodeagent/mfmasweep.h.
+DEFAULT_MFMA_SWEEP_SEED = 0x4D493335_35584D53
+MFMA_SWEEP_DTYPES = {"bf16": 0, "fp8": 1}
+MFMA_SWEEP_WAVES_PER_WG = 4
+MFMA_SWEEP_MAX_LISTED = 8
+NO_BAD_WAVE = (1 << 64) - 1
+# bf16 floor of the default sweep: 0.70 x the 2282.1 TFLOP/s median measured
+# on MI355X (profiles/mfma_sweep_mi355x.txt); the margin covers the 12 %
+# device-to-device spread of MFMA-only loops. Integer operands held in
+# registers clock higher than a random-data GEMM, so the figure is NOT
+# comparable to GEMM benchmarks. 0 disables the floor.
+MIN_MFMA_SWEEP_TFLOPS = 1597.5
 
 
 class NodeAgentError(RuntimeError):
@@ -91,6 +105,87 @@ class MemtestResult:
         )
 
 
+class MfmaRecord(ctypes.Structure):
+    """One wave of the matrix-core sweep (``na_mfma_record``): its checksum,
+    the s_memtime / s_memrealtime deltas around its fold loop, its global
+    wave index and the unit it ran on."""
+
+    _fields_ = [
+        ("checksum", ctypes.c_uint64),
+        ("cycles", ctypes.c_uint64),
+        ("realtime", ctypes.c_uint64),
+        ("wave", ctypes.c_uint32),
+        ("xcc", ctypes.c_uint32),
+        ("se", ctypes.c_uint32),
+        ("sh", ctypes.c_uint32),
+        ("cu", ctypes.c_uint32),
+        ("simd", ctypes.c_uint32),
+    ]
+
+
+class _MfmaSweepResultC(ctypes.Structure):
+    _fields_ = [
+        ("waves", ctypes.c_uint64),
+        ("bad_waves", ctypes.c_uint64),
+        ("units_seen", ctypes.c_uint64),
+        ("bad_units", ctypes.c_uint64),
+        ("first_bad_wave", ctypes.c_uint64),
+        ("clock_mhz", ctypes.c_double),
+        ("first_bad_unit", ctypes.c_uint32 * 5),
+        ("listed", ctypes.c_uint32),
+        ("bad_list", (ctypes.c_uint32 * 5) * MFMA_SWEEP_MAX_LISTED),
+    ]
+
+
+def mfma_unit_name(unit) -> str:
+    """``(xcc, se, sh, cu[, simd])`` -> ``xcc2.se1.sh0.cu5[.simd3]``: the
+    XCD, shader engine and shader array within it, CU within the array, and
+    SIMD within the CU, as the hardware's XCC_ID / HW_ID registers number
+    them."""
+    name = "xcc{}.se{}.sh{}.cu{}".format(*unit[:4])
+    return name + (f".simd{unit[4]}" if len(unit) > 4 else "")
+
+
+@dataclass
+class MfmaSweepResult:
+    """Outcome of a sweep verify. A *unit* is a CU, ``(xcc, se, sh, cu)``;
+    ``bad_simds`` lists the first distinct failing ``(xcc, se, sh, cu, simd)``
+    (at most ``MFMA_SWEEP_MAX_LISTED``), the first being the unit of
+    ``first_bad_wave``. ``tflops`` is 0 when only a verify was done."""
+
+    dtype: str = "bf16"
+    waves: int = 0
+    bad_waves: int = 0
+    units_seen: int = 0
+    bad_units: int = 0
+    first_bad_wave: int = NO_BAD_WAVE
+    bad_simds: list = field(default_factory=list)
+    clock_mhz: float = 0.0
+    tflops: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.bad_waves == 0
+
+    def describe(self) -> str:
+        simds: dict = {}  # CU -> its failing SIMDs, in order of first failure
+        for u in self.bad_simds:
+            simds.setdefault(tuple(u[:4]), []).append(str(u[4]))
+        names = ", ".join(f"{mfma_unit_name(cu)} simd {','.join(s)}" for cu, s in simds.items())
+        more = ", ..." if len(self.bad_simds) == MFMA_SWEEP_MAX_LISTED else ""
+        return (
+            f"{self.bad_waves} of {self.waves} waves wrong on {self.bad_units} CU(s): "
+            f"{names}{more}"
+        )
+
+    @classmethod
+    def _from_c(cls, dtype: str, res: "_MfmaSweepResultC", tflops: float = 0.0):
+        return cls(
+            dtype, res.waves, res.bad_waves, res.units_seen, res.bad_units, res.first_bad_wave,
+            [tuple(res.bad_list[i]) for i in range(res.listed)], res.clock_mhz, tflops,
+        )
+
+
 def _load_lib() -> ctypes.CDLL:
     for p in _SEARCH_PATHS:
         if os.path.exists(p):
@@ -123,6 +218,12 @@ class GPUReport:
     hbm_memtest_bad_words: int = 0
     hbm_memtest_gbs: float = 0.0
     hbm_memtest_skipped: str = ""  # reason, when requested but not run
+    # chip-wide matrix-core sweep (opt-in; all "not run" by default)
+    mfma_sweep_tflops: float = 0.0
+    mfma_sweep_fp8_tflops: float = 0.0
+    mfma_sweep_clock_mhz: float = 0.0  # bf16 run; informational, no floor
+    mfma_sweep_units_seen: int = 0
+    mfma_sweep_bad_waves: int = 0
 
 
 @dataclass
@@ -311,6 +412,93 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"HBM memtest: {res.describe()}")
 
+    # -- chip-wide matrix-core sweep ------------------------------------------
+
+    @staticmethod
+    def _mfma_dtype(dtype: str) -> int:
+        if dtype not in MFMA_SWEEP_DTYPES:
+            raise NodeAgentError(f"mfma sweep: dtype {dtype!r} is not one of bf16, fp8")
+        return MFMA_SWEEP_DTYPES[dtype]
+
+    def mfma_sweep_expected(self, wave: int, outer: int,
+                            seed: int = DEFAULT_MFMA_SWEEP_SEED) -> int:
+        """Checksum wave ``wave`` must report after ``outer`` folds (host
+        arithmetic only; needs no GPU)."""
+        out = ctypes.c_uint64(0)
+        rc = self.lib.na_mfma_sweep_expected(
+            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"mfma_sweep_expected: {self._err()}")
+        return out.value
+
+    def mfma_sweep_run(self, dev: int, dtype: str = "bf16", workgroups: int = 1,
+                       outer: int = 1, seed: int = DEFAULT_MFMA_SWEEP_SEED) -> tuple:
+        """One launch of ``workgroups`` x 4 waves, each through ``outer``
+        folds of 64 MFMAs. Returns ``(records, ms)``: a ctypes array of
+        ``MfmaRecord`` (record i is wave i) and the HIP-event time."""
+        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
+        recs = (MfmaRecord * max(n, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_mfma_sweep_run(
+            dev, self._mfma_dtype(dtype), workgroups, outer, ctypes.c_ulonglong(seed),
+            recs, ctypes.c_longlong(n), ctypes.byref(ms),
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"mfma_sweep_run({dev}): {self._err()}")
+        return recs, ms.value
+
+    def mfma_sweep_verify(self, recs, outer: int, seed: int = DEFAULT_MFMA_SWEEP_SEED,
+                          dtype: str = "bf16") -> tuple:
+        """Compare every record against the host reference. Returns
+        ``(rc, MfmaSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad wave,
+        and ``na_last_error`` then names the first failing unit."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_mfma_sweep_verify(
+            recs, ctypes.c_longlong(len(recs)), outer, ctypes.c_ulonglong(seed),
+            ctypes.byref(res),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, MfmaSweepResult(dtype)
+        return rc, MfmaSweepResult._from_c(dtype, res)
+
+    def mfma_sweep(self, dev: int, dtype: str = "bf16", workgroups: int = 0, outer: int = 0,
+                   seed: int = DEFAULT_MFMA_SWEEP_SEED) -> MfmaSweepResult:
+        """Run one wave per SIMD on every CU through a long MFMA chain
+        (``workgroups`` 0 = 4 per CU, ``outer`` 0 = the default fold count),
+        verify every wave bit-exactly against the host reference, and
+        report sustained TFLOP/s and the in-kernel clock. Wrong waves come
+        back in the result (``.ok`` False) with the units they ran on, not
+        as an exception. The TFLOP/s figure is on small-integer operands held
+        in registers and is not comparable to GEMM benchmarks."""
+        res = _MfmaSweepResultC()
+        tflops = ctypes.c_double(0)
+        rc = self.lib.na_mfma_sweep(
+            dev, self._mfma_dtype(dtype), workgroups, outer, ctypes.c_ulonglong(seed),
+            ctypes.byref(res), ctypes.byref(tflops),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            raise NodeAgentError(f"mfma_sweep({dev}, {dtype}): {self._err()}")
+        return MfmaSweepResult._from_c(dtype, res, tflops.value)
+
+    def _run_mfma_sweep(self, g: GPUReport) -> None:
+        for dtype in ("bf16", "fp8"):
+            res = self.mfma_sweep(g.index, dtype)
+            g.mfma_sweep_bad_waves += res.bad_waves
+            if dtype == "bf16":
+                g.mfma_sweep_tflops = round(res.tflops, 1)
+                g.mfma_sweep_clock_mhz = round(res.clock_mhz, 1)
+                g.mfma_sweep_units_seen = res.units_seen
+                if res.tflops < MIN_MFMA_SWEEP_TFLOPS:
+                    g.problems.append(
+                        f"MFMA sweep bf16 {g.mfma_sweep_tflops} TFLOP/s below floor "
+                        f"{MIN_MFMA_SWEEP_TFLOPS}"
+                    )
+            else:
+                g.mfma_sweep_fp8_tflops = round(res.tflops, 1)
+            if not res.ok:
+                g.problems.append(f"MFMA sweep {dtype}: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         if self.lib.na_p2p_matrix(n, buf) != 0:
@@ -329,13 +517,19 @@ class NodeAgent:
     # -- full health check ---------------------------------------------------
 
     def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
-              memtest_bytes: int = 0) -> NodeReport:
+              memtest_bytes: int = 0, mfma_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
         reason lands in ``hbm_memtest_skipped`` and the GPU stays healthy.
         Regions under 512 MiB are allowed but are served largely from the
-        256 MiB Infinity Cache, not DRAM. 0 (default) runs nothing new."""
+        256 MiB Infinity Cache, not DRAM. 0 (default) runs nothing new.
+
+        ``mfma_sweep`` additionally runs the chip-wide matrix-core sweep in
+        bf16 and fp8 on every GPU: a wrong wave is a problem that names the
+        unit it ran on, as is a bf16 rate under ``MIN_MFMA_SWEEP_TFLOPS``.
+        ``mfma_sweep_units_seen`` below the CU count is reported, not a
+        problem. False (default) makes no sweep call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -388,6 +582,8 @@ class NodeAgent:
                     )
                 if memtest_bytes > 0:
                     self._run_memtest(g, memtest_bytes)
+                if mfma_sweep:
+                    self._run_mfma_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -484,6 +680,14 @@ def main(argv=None) -> int:
         "allowed but are served largely from the 256 MiB Infinity Cache, not DRAM",
     )
     ap.add_argument(
+        "--mfma-sweep",
+        action="store_true",
+        help="also run the chip-wide matrix-core sweep on every GPU: one wave per SIMD of "
+        "every CU through a long bf16 and fp8 MFMA chain, each wave checked bit-exactly and "
+        "a wrong one attributed to its XCC/SE/SH/CU/SIMD; reports sustained TFLOP/s "
+        "(integer operands: not comparable to GEMM benchmarks) and the in-kernel clock",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -496,6 +700,7 @@ def main(argv=None) -> int:
             expect_gpus=args.expect_gpus,
             bw_bytes=args.bw_bytes,
             memtest_bytes=args.memtest_bytes,
+            mfma_sweep=args.mfma_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

@@ -8,7 +8,8 @@
 // reach ~6 TB/s of the 8 TB/s peak), an opt-in HBM data-integrity test
 // (pattern fill / verify+invert / verify, memtest.h), a VALU FMA correctness check, an MFMA
 // matrix-pipe check (v_mfma_f32_16x16x4_f32 — the CDNA4 matrix core the ML
-// workloads will live on), and the xGMI peer-to-peer link matrix.
+// workloads will live on), an opt-in chip-wide matrix-core sweep (one wave
+// per SIMD of every CU, mfmasweep.h), and the xGMI peer-to-peer link matrix.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
 // consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
@@ -16,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -981,4 +983,245 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
 extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned long long seed,
                               na_memtest_result* out, double* gbs) {
     return na_hbm_memtest_passes(dev, bytes, rounds, seed, out, gbs, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide matrix-core sweep (kernel in mfmasweep.h)
+// ---------------------------------------------------------------------------
+//
+// Every MFMA check above is one wave: one SIMD of one CU. The sweep runs one
+// wave per SIMD on every CU, each through `outer` folds of 64 MFMAs on its
+// own integer data, and the host recomputes every wave's checksum exactly, so
+// a bad matrix core is named by (XCC, SE, SH, CU, SIMD). The timed launch
+// also yields sustained TFLOP/s and the in-kernel clock. The figure comes
+// from small-integer operands held in registers, which clock higher than a
+// random-data GEMM: it is a health floor, not a GEMM benchmark.
+
+#include "mfmasweep.h"
+
+#define NA_MFMA_MAX_LISTED 8
+#define NA_MFMA_MAX_WORKGROUPS (1 << 20)
+#define NA_MFMA_MAX_OUTER (1 << 22)  // ~2 s per resident wave: keeps a typo from hanging the node
+// 8192 folds x 64 MFMAs x 16 cycles is ~3.5 ms per workgroup at 2.4 GHz, and
+// the default grid puts four workgroups on each CU in turn: ~14 ms by
+// arithmetic, 15.4 ms (bf16) / 16.1 ms (fp8) measured
+// (profiles/mfma_sweep_mi355x.txt) — past the 10 ms from which the
+// in-kernel clock estimate is reliable.
+#define NA_MFMA_DEFAULT_OUTER 8192
+
+typedef struct {
+    uint64_t waves, bad_waves;
+    uint64_t units_seen, bad_units;  // distinct (xcc, se, sh, cu)
+    uint64_t first_bad_wave;         // UINT64_MAX = none
+    double clock_mhz;                // median of cycles / realtime x 100 MHz
+    uint32_t first_bad_unit[5];      // xcc, se, sh, cu, simd
+    uint32_t listed;                 // entries used in bad_list
+    uint32_t bad_list[NA_MFMA_MAX_LISTED][5];  // first distinct failing (xcc, se, sh, cu, simd)
+} na_mfma_sweep_result;
+
+// S(n) = sum_{j<n} q^j mod 2^64 by binary expansion of n.
+static uint64_t ms_geometric_sum(uint64_t q, uint64_t n) {
+    uint64_t s = 0, qk = 1;  // s = S(k), qk = q^k for the bits of n consumed so far
+    for (int bit = 63; bit >= 0; --bit) {
+        s *= 1 + qk;
+        qk *= qk;
+        if ((n >> bit) & 1) {
+            s = s * q + 1;
+            qk *= q;
+        }
+    }
+    return s;
+}
+
+// sum over the wave's 64 lanes of P = d0 G^3 + d1 G^2 + d2 G + d3, where
+// d_i = D[(l>>4)*4+i][l&15] and D = (sum_t A_t)(sum_t B_t).
+static uint64_t ms_wave_p_sum(uint64_t base, uint64_t wave) {
+    int sa[16][32], sb[16][32];
+    for (int r = 0; r < 16; ++r) {
+        for (int k = 0; k < 32; ++k) {
+            sa[r][k] = sb[r][k] = 0;
+            for (int t = 0; t < MS_FRAGS; ++t) {
+                sa[r][k] += ms_value(base, wave, 0, t, r, k);
+                sb[r][k] += ms_value(base, wave, 1, t, r, k);
+            }
+        }
+    }
+    uint64_t sum = 0;
+    for (int l = 0; l < 64; ++l) {
+        uint64_t p = 0;
+        for (int i = 0; i < 4; ++i) {
+            int row = (l >> 4) * 4 + i, col = l & 15, d = 0;
+            for (int k = 0; k < 32; ++k) d += sa[row][k] * sb[col][k];
+            p = p * MS_G + (uint64_t)(int64_t)d;
+        }
+        sum += p;
+    }
+    return sum;
+}
+
+// Pure host code. All folds produce the same D, so the per-lane recurrence
+// c = c G + d_i collapses to c = P S(outer), S(n) = sum_{j<n} G^{4j}, and the
+// wave checksum to S(outer) * sum_l P_l.
+extern "C" int na_mfma_sweep_expected(unsigned long long seed, unsigned long long wave, int outer,
+                                      uint64_t* checksum) {
+    if (outer < 1 || checksum == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_mfma_sweep_expected: need outer >= 1 (got %d) and a result pointer",
+                      outer);
+        return NA_ERR_ARG;
+    }
+    const uint64_t g2 = MS_G * MS_G;
+    *checksum = ms_geometric_sum(g2 * g2, (uint64_t)outer) * ms_wave_p_sum(seed * MS_G, wave);
+    return NA_OK;
+}
+
+// Everything a sweep launch owns; the destructor frees it on every path.
+struct ms_launch {
+    na_mfma_record* d = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~ms_launch() {
+        if (d) (void)hipFree(d);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// One launch of `workgroups` x 4 waves, HIP-event timed; out receives the
+// 4 * workgroups records. Argument errors are detected before any HIP call.
+extern "C" int na_mfma_sweep_run(int dev, int dtype, int workgroups, int outer,
+                                 unsigned long long seed, na_mfma_record* out, long long n_out,
+                                 double* ms) {
+    if ((dtype != MS_BF16 && dtype != MS_FP8) || workgroups < 1 ||
+        workgroups > NA_MFMA_MAX_WORKGROUPS || outer < 1 || outer > NA_MFMA_MAX_OUTER ||
+        out == nullptr || n_out < (long long)workgroups * MS_WAVES_PER_WG) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_mfma_sweep_run: need dtype 0 (bf16) or 1 (fp8) (got %d), workgroups in "
+                      "1..%d (got %d), outer in 1..%d (got %d) and room for 4 records per "
+                      "workgroup (out %p, n_out %lld)",
+                      dtype, NA_MFMA_MAX_WORKGROUPS, workgroups, NA_MFMA_MAX_OUTER, outer,
+                      (void*)out, n_out);
+        return NA_ERR_ARG;
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    // the whole per-workgroup allocation, as na_lds_selftest launches with:
+    // more than half of the CU's LDS, so one workgroup per CU
+    size_t lds_bytes = prop.sharedMemPerBlock;
+    if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
+    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
+    ms_launch run;
+    HIP_CHECK(hipMalloc(&run.d, n * sizeof(na_mfma_record)));
+    // a record its wave never wrote carries no valid wave index and fails the verify
+    HIP_CHECK(hipMemset(run.d, 0xFF, n * sizeof(na_mfma_record)));
+    for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventCreate(&run.ev[i]));
+    const mt_u64 base = seed * MS_G;
+    dim3 grid((unsigned)workgroups), block(MS_BLOCK);
+    HIP_CHECK(hipEventRecord(run.ev[0]));
+    if (dtype == MS_BF16)
+        mfma_sweep_kernel<MS_BF16><<<grid, block, lds_bytes>>>(run.d, base, outer);
+    else
+        mfma_sweep_kernel<MS_FP8><<<grid, block, lds_bytes>>>(run.d, base, outer);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(run.ev[1]));
+    HIP_CHECK(hipEventSynchronize(run.ev[1]));
+    float elapsed = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&elapsed, run.ev[0], run.ev[1]));
+    HIP_CHECK(hipMemcpy(out, run.d, n * sizeof(na_mfma_record), hipMemcpyDeviceToHost));
+    if (ms) *ms = (double)elapsed;
+    return NA_OK;
+}
+
+static inline uint32_t ms_cu_key(const na_mfma_record& r) {
+    return ((r.xcc & 15) << 7) | ((r.se & 3) << 5) | ((r.sh & 1) << 4) | (r.cu & 15);
+}
+
+// Pure host code: record i is wave i. A wave is bad when its checksum is
+// not the expected one or it does not carry its own index. Returns
+// NA_ERR_VERIFY on any bad wave; *res is filled either way.
+extern "C" int na_mfma_sweep_verify(const na_mfma_record* recs, long long n, int outer,
+                                    unsigned long long seed, na_mfma_sweep_result* res) {
+    if (recs == nullptr || n < 1 || outer < 1 || res == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_mfma_sweep_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) "
+                      "and a result pointer",
+                      n, outer);
+        return NA_ERR_ARG;
+    }
+    std::memset(res, 0, sizeof(*res));
+    res->waves = (uint64_t)n;
+    res->first_bad_wave = UINT64_MAX;
+    const uint64_t base = seed * MS_G, g2 = MS_G * MS_G;
+    const uint64_t s = ms_geometric_sum(g2 * g2, (uint64_t)outer);
+    std::vector<bool> seen(1 << 11, false), bad(1 << 11, false);
+    std::vector<double> mhz;
+    mhz.reserve((size_t)n);
+    for (long long i = 0; i < n; ++i) {
+        const na_mfma_record& r = recs[i];
+        const uint32_t key = ms_cu_key(r);
+        if (!seen[key]) {
+            seen[key] = true;
+            res->units_seen++;
+        }
+        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
+        if (r.checksum == s * ms_wave_p_sum(base, (uint64_t)i) && r.wave == (uint64_t)i) continue;
+        res->bad_waves++;
+        if (!bad[key]) {
+            bad[key] = true;
+            res->bad_units++;
+        }
+        const uint32_t unit[5] = {r.xcc, r.se, r.sh, r.cu, r.simd};
+        if (res->first_bad_wave == UINT64_MAX) {
+            res->first_bad_wave = (uint64_t)i;
+            std::memcpy(res->first_bad_unit, unit, sizeof(unit));
+        }
+        bool listed = false;
+        for (uint32_t k = 0; k < res->listed && !listed; ++k)
+            listed = std::memcmp(res->bad_list[k], unit, sizeof(unit)) == 0;
+        if (!listed && res->listed < NA_MFMA_MAX_LISTED)
+            std::memcpy(res->bad_list[res->listed++], unit, sizeof(unit));
+    }
+    if (!mhz.empty()) {
+        std::nth_element(mhz.begin(), mhz.begin() + mhz.size() / 2, mhz.end());
+        res->clock_mhz = mhz[mhz.size() / 2];
+    }
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                  "mfma sweep: %llu of %llu waves wrong on %llu CU(s), first wave %llu on "
+                  "xcc%u.se%u.sh%u.cu%u.simd%u",
+                  (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                  (unsigned long long)res->bad_units, (unsigned long long)res->first_bad_wave,
+                  u[0], u[1], u[2], u[3], u[4]);
+    return NA_ERR_VERIFY;
+}
+
+// Whole sweep: one untimed warm-up launch, the timed launch, the verify.
+// workgroups 0 = 4 per CU, outer 0 = NA_MFMA_DEFAULT_OUTER. *tflops counts
+// 64 MFMAs of 16384 FLOP per wave and fold over the event time.
+extern "C" int na_mfma_sweep(int dev, int dtype, int workgroups, int outer,
+                             unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
+    if (res == nullptr || workgroups < 0 || workgroups > NA_MFMA_MAX_WORKGROUPS || outer < 0) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_mfma_sweep: need workgroups in 0..%d (got %d), outer >= 0 (got %d) and "
+                      "a result pointer",
+                      NA_MFMA_MAX_WORKGROUPS, workgroups, outer);
+        return NA_ERR_ARG;
+    }
+    if (outer == 0) outer = NA_MFMA_DEFAULT_OUTER;
+    if (workgroups == 0) {
+        hipDeviceProp_t prop;
+        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+        workgroups = 4 * prop.multiProcessorCount;
+    }
+    std::vector<na_mfma_record> recs((size_t)workgroups * MS_WAVES_PER_WG);
+    double ms = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
+        int rc = na_mfma_sweep_run(dev, dtype, workgroups, outer, seed, recs.data(),
+                                   (long long)recs.size(), &ms);
+        if (rc != NA_OK) return rc;
+    }
+    if (tflops)
+        *tflops = (double)recs.size() * outer * MS_MFMA_PER_FOLD * MS_FLOP_PER_MFMA / (ms * 1e9);
+    return na_mfma_sweep_verify(recs.data(), (long long)recs.size(), outer, seed, res);
 }

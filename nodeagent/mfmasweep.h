@@ -1,0 +1,195 @@
+// Chip-wide matrix-core sweep for the MI355X node agent (included from
+// agent.hip, after the MFMA vector typedefs and e4m3()).
+//
+// The single-wave MFMA checks in agent.hip run on one SIMD of one CU. This
+// kernel puts one wave on every SIMD of every CU, has each run a long MFMA
+// chain on its own data, and leaves one record per wave: a checksum of every
+// product it computed, the physical unit it ran on, and two clock deltas.
+// The host recomputes each wave's checksum exactly, so a wrong wave is
+// attributed to (XCC, SE, SH, CU, SIMD).
+//
+// Operands (normative — tests/test_nodeagent_mfmasweep.py carries an
+// independent numpy copy); arithmetic mod 2^64, G = 0x9E3779B97F4A7C15,
+// mix64 = mt_mix64 of memtest.h. For global wave w = blockIdx.x*4 +
+// (threadIdx.x>>6), matrix m (0 = A, 1 = B), fragment t in 0..7, r in 0..15
+// (row of A / column of B) and k in 0..31:
+//
+//   idx = (((w*2 + m)*8 + t)*16 + r)*32 + k
+//   e   = mix64(seed*G + idx)
+//   A   = ((e >> 40) % 7) - 3          B = ((e >> 40) % 5) - 2
+//
+// Per-lane layout as in mfma_bf16_tile_kernel (A: row l&15, k = (l>>4)*8+i;
+// B: col l&15, same k; D: col l&15, row (l>>4)*4+i). Small integers are
+// exact in bf16 and in E4M3, every partial sum is an exact f32 integer
+// (|D| <= 12288), so bf16 and fp8 give the same checksums in any order.
+//
+// One fold = every A fragment times every B fragment = 64 MFMAs, i.e.
+// D = (sum_t A_t)(sum_t B_t). After each fold, per lane and for i = 0..3:
+//   c = c*G + (uint64)(int64)D[(l>>4)*4+i][l&15]
+// The wave checksum is sum_l c_l.
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "memtest.h"
+
+#define MS_BLOCK 256  // four waves: one per SIMD of the CU
+#define MS_WAVES_PER_WG (MS_BLOCK / 64)
+#define MS_FRAGS 8
+#define MS_MFMA_PER_FOLD (MS_FRAGS * MS_FRAGS)
+#define MS_FLOP_PER_MFMA 16384.0  // 16 x 16 x 32 x 2
+#define MS_G 0x9E3779B97F4A7C15ULL
+
+enum { MS_BF16 = 0, MS_FP8 = 1 };
+
+// s_getreg operand: SIZE-1 in 15:11, OFFSET in 10:6, register id in 5:0
+// (encodings: amd_device_functions.h). HW_ID is register 4, XCC_ID 20.
+#define MS_GETREG(size, offset, reg) ((((size)-1) << 11) | ((offset) << 6) | (reg))
+
+// One per wave, written by one lane. cycles/realtime are the deltas of
+// s_memtime (shader clock) and s_memrealtime (100 MHz) around the fold loop.
+typedef struct {
+    uint64_t checksum, cycles, realtime;
+    uint32_t wave, xcc, se, sh, cu, simd;
+} na_mfma_record;
+
+__device__ __host__ inline int ms_value(mt_u64 base, mt_u64 w, int m, int t, int r, int k) {
+    mt_u64 idx = ((((w * 2 + (mt_u64)m) * 8 + (mt_u64)t) * 16 + (mt_u64)r) * 32 + (mt_u64)k);
+    unsigned e = (unsigned)(mt_mix64(base + idx) >> 40);  // 24 bits
+    return m == 0 ? (int)(e % 7u) - 3 : (int)(e % 5u) - 2;
+}
+
+#if defined(__gfx950__)
+
+template <int DTYPE>
+struct ms_frag;
+template <>
+struct ms_frag<MS_BF16> {
+    typedef bf16x8 type;
+};
+template <>
+struct ms_frag<MS_FP8> {
+    typedef long type;  // 8 packed E4M3 bytes, element i at byte i
+};
+
+__device__ inline void ms_set(bf16x8& f, int i, int v) { f[i] = (__bf16)(float)v; }
+// e4m3()'s seven encodings packed into one constant (folded at compile
+// time), so the fragment set-up stays branch-free.
+__device__ inline void ms_set(long& f, int i, int v) {
+    mt_u64 table = 0;
+#pragma unroll
+    for (int x = -3; x <= 3; ++x) table |= (mt_u64)e4m3(x) << (8 * (x + 3));
+    f |= (long)((table >> (8 * (v + 3))) & 0xFF) << (8 * i);
+}
+
+__device__ inline f32x4 ms_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ inline f32x4 ms_mfma(long a, long b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+}
+
+// One fold. The operands never change, so without the empty asm the
+// compiler may compute D once and drop the loop; "+v" tells it each A
+// fragment might have, at no instruction. One accumulation chain: this shape
+// issues back to back at the same ~16 cycles on 1, 4 or 16 accumulators, and
+// a single one leaves nothing to sum after the last MFMA.
+template <typename FRAG>
+__device__ inline f32x4 ms_fold(FRAG (&a)[MS_FRAGS], const FRAG (&b)[MS_FRAGS]) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ta = 0; ta < MS_FRAGS; ++ta) {
+        asm volatile("" : "+v"(a[ta]));
+#pragma unroll
+        for (int tb = 0; tb < MS_FRAGS; ++tb) acc = ms_mfma(a[ta], b[tb], acc);
+    }
+    return acc;
+}
+
+__device__ inline mt_u64 ms_update(mt_u64 c, f32x4 d) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c = c * MS_G + (mt_u64)(long long)(int)d[i];
+    return c;
+}
+
+#endif  // __gfx950__
+
+// records: 4 * gridDim.x entries. base = seed * G (hoisted to the host).
+// Launch with MS_BLOCK threads and more than half of the CU's LDS as dynamic
+// shared memory.
+template <int DTYPE>
+__global__ void __launch_bounds__(MS_BLOCK)
+mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) {
+#if defined(__gfx950__)
+    // The dynamic LDS is a placement device and is never touched: a
+    // workgroup that holds more than half of a CU's LDS cannot share the CU
+    // with a second one, so each of its four waves has a SIMD to itself —
+    // the condition for back-to-back 16-cycle issue of this MFMA shape.
+    typedef typename ms_frag<DTYPE>::type frag;
+    const unsigned hw_id = __builtin_amdgcn_s_getreg(MS_GETREG(32, 0, 4));
+    const unsigned xcc_id = __builtin_amdgcn_s_getreg(MS_GETREG(4, 0, 20));
+    const int l = threadIdx.x & 63;
+    const mt_u64 w = (mt_u64)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6);
+
+    frag a[MS_FRAGS], b[MS_FRAGS];
+    const int r = l & 15, k0 = (l >> 4) * 8;
+#pragma unroll
+    for (int t = 0; t < MS_FRAGS; ++t) {
+        a[t] = frag{};
+        b[t] = frag{};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            ms_set(a[t], i, ms_value(base, w, 0, t, r, k0 + i));
+            ms_set(b[t], i, ms_value(base, w, 1, t, r, k0 + i));
+        }
+    }
+
+    // The stamps bracket the whole loop, go only into the record, and no
+    // output is computed from them.
+    __builtin_amdgcn_sched_barrier(0);
+    const mt_u64 t0 = __builtin_amdgcn_s_memtime();
+    const mt_u64 rt0 = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_sched_barrier(0);
+
+    // Software-pipelined by one fold: the checksum update of fold j-1 does
+    // not depend on fold j's MFMAs, so its VALU work issues in their shadow.
+    mt_u64 c = 0;
+    f32x4 d = ms_fold(a, b);
+    for (int j = 1; j < outer; ++j) {
+        f32x4 dn = ms_fold(a, b);
+        c = ms_update(c, d);
+        d = dn;
+    }
+    c = ms_update(c, d);
+
+    __builtin_amdgcn_sched_barrier(0);
+    const mt_u64 t1 = __builtin_amdgcn_s_memtime();
+    const mt_u64 rt1 = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_sched_barrier(0);
+
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if (l == 0) {
+        na_mfma_record rec;
+        rec.checksum = c;
+        rec.cycles = t1 - t0;
+        rec.realtime = rt1 - rt0;
+        rec.wave = (uint32_t)w;
+        rec.xcc = xcc_id & 15;
+        rec.se = (hw_id >> 13) & 3;
+        rec.sh = (hw_id >> 12) & 1;
+        rec.cu = (hw_id >> 8) & 15;
+        rec.simd = (hw_id >> 4) & 3;
+        records[w] = rec;
+    }
+#else
+    // wrong arch: a checksum no reference produces, so verification fails
+    if ((threadIdx.x & 63) == 0) {
+        na_mfma_record rec = {};
+        rec.checksum = ~0ULL;
+        records[(size_t)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6)] = rec;
+    }
+#endif
+}
