@@ -6,6 +6,7 @@ VERSION ?= 0.1.0
 IMAGE ?= ghcr.io/kaito-project/gpu-provisioner-amd:$(VERSION)
 PYTHON ?= python
 HIPCC ?= hipcc
+CXX ?= c++
 OFFLOAD_ARCH ?= gfx950
 
 AZURE_SUBSCRIPTION_ID ?=
@@ -14,19 +15,30 @@ AZURE_CLUSTER_NAME ?= gpu-provisioner-amd-aks
 AZURE_LOCATION ?= eastus2
 IDENTITY_NAME ?= gpu-provisioner-amd-id
 
-.PHONY: all build nodeagent unit-test gpu-test e2etests bench lint lint-full clean \
+.PHONY: all build nodeagent jsontree unit-test gpu-test e2etests bench lint lint-full clean \
         docker-build docker-build-multiarch helm-template \
         az-mkrg az-mkaks az-identity az-federated-credential az-patch-helm
 
 all: build
 
-build: nodeagent
+build: nodeagent jsontree
 
 nodeagent: gpu_provisioner_amd/_native/libmi355x_nodeagent.so
 
 gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip nodeagent/memtest.h nodeagent/mfmasweep.h
 	mkdir -p gpu_provisioner_amd/_native
 	$(HIPCC) --offload-arch=$(OFFLOAD_ARCH) -O3 -shared -fPIC $< -o $@
+
+# CPython extension for the JSON-tree walks (deep copy, merge patch, CRD
+# validation verdict); the package falls back to pure Python without it
+JSONTREE_SO := gpu_provisioner_amd/_native/_jsontree$(shell $(PYTHON) -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
+
+jsontree: $(JSONTREE_SO)
+
+$(JSONTREE_SO): native/jsontree.cpp
+	mkdir -p gpu_provisioner_amd/_native
+	$(CXX) -O2 -std=c++17 -shared -fPIC \
+	  -I$$($(PYTHON) -c "import sysconfig; print(sysconfig.get_paths()['include'])") $< -o $@
 
 unit-test:
 	$(PYTHON) -m pytest tests/ -q -m "not gpu"

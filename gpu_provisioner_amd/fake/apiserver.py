@@ -40,6 +40,7 @@ from ..kube.client import (
     NotFoundError,
     json_merge_patch,
     match_field_selector,
+    merge_patch_owned,
 )
 
 _WATCH_HISTORY = 4096  # events kept for resourceVersion resume
@@ -252,12 +253,17 @@ class InMemoryAPIServer:
                 )
             return self._apply_update(gvk, key, cur, obj, subresource)
 
-    def _apply_update(self, gvk: tuple, key: tuple, cur: dict, obj: dict, subresource: str) -> dict:
+    def _apply_update(
+        self, gvk: tuple, key: tuple, cur: dict, obj: dict, subresource: str, owned: bool = False
+    ) -> dict:
         # Revision objects are immutable: a new revision may SHARE unchanged
         # subtrees with the previous one (they are never mutated in place),
         # so a status write is a shallow re-root + one status copy, not a
         # full-object copy. Caller-provided data is still deep-copied — the
         # caller retains its reference and may mutate it afterwards.
+        # `owned` (patch): obj was built by merge_patch_owned, which already
+        # copied what came from the caller and shares the rest with `cur`;
+        # its top level and metadata are fresh, so it is taken as it is.
         if subresource == "status":
             stored = {**cur, "metadata": {**cur["metadata"]}}
             stored["status"] = ko.deep_copy(obj.get("status", {}))
@@ -273,7 +279,7 @@ class InMemoryAPIServer:
                         "metadata.finalizers: Forbidden: no new finalizers can "
                         f"be added if the object is being deleted (added: {sorted(added)})"
                     )
-            new = ko.deep_copy(obj)
+            new = obj if owned else ko.deep_copy(obj)
             # status is a subresource: ignore status changes on main-resource update
             new["status"] = cur.get("status", {})
             # immutable metadata
@@ -284,14 +290,19 @@ class InMemoryAPIServer:
                     nm[f] = cm[f]
                 else:
                     nm.pop(f, None)
-            if new.get("spec") != cur.get("spec"):
+            ns, cs = new.get("spec"), cur.get("spec")
+            if ns is cs:
+                # spec subtree shared with the previous revision (a patch
+                # that left it alone): nothing to compare or repair
+                pass
+            elif ns != cs:
                 nm["generation"] = cm.get("generation", 1) + 1
             elif "spec" in new:
                 # re-share the unchanged spec subtree with the previous
                 # revision: deep_copy broke identity, and identity is what
                 # lets the CRD validator's changed-only walk (and any other
                 # revision differ) prune in O(1) instead of deep-comparing
-                new["spec"] = cur.get("spec")
+                new["spec"] = cs
             stored = new
         self._validate(gvk, stored, cur)  # CRD schema + CEL immutability (422)
         self._bump(stored)
@@ -332,9 +343,11 @@ class InMemoryAPIServer:
             if subresource == "status":
                 merged_status = json_merge_patch(cur.get("status", {}), patch.get("status", patch))
                 return self._apply_update(gvk, key, cur, {"status": merged_status}, "status")
-            merged = json_merge_patch(cur, patch)
+            # fused merge + ownership: only what the caller's patch brings
+            # is copied, untouched subtrees of `cur` keep their identity
+            merged = merge_patch_owned(cur, patch)
             merged.setdefault("metadata", {})["resourceVersion"] = cur["metadata"]["resourceVersion"]
-            return self._apply_update(gvk, key, cur, merged, "")
+            return self._apply_update(gvk, key, cur, merged, "", owned=True)
 
     async def delete(
         self,

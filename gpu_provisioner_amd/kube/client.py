@@ -16,6 +16,8 @@ import abc
 import re
 from typing import Any, AsyncIterator, Optional, Sequence
 
+from .objects import _native_jsontree, _py_deep_copy
+
 
 # ---------------------------------------------------------------------------
 # Error taxonomy (mirrors apimachinery k8serrors the reference branches on)
@@ -290,7 +292,7 @@ class KubeClient(abc.ABC):
 # ---------------------------------------------------------------------------
 
 
-def json_merge_patch(target: dict, patch: dict) -> dict:
+def _py_json_merge_patch(target: dict, patch: dict) -> dict:
     """Apply RFC 7386 merge patch, returning a new dict."""
     if not isinstance(patch, dict):
         return patch
@@ -299,7 +301,45 @@ def json_merge_patch(target: dict, patch: dict) -> dict:
         if v is None:
             out.pop(k, None)
         elif isinstance(v, dict):
-            out[k] = json_merge_patch(out.get(k, {}), v)
+            out[k] = _py_json_merge_patch(out.get(k, {}), v)
         else:
             out[k] = v
     return out
+
+
+def _py_merge_owned(target, patch):
+    if not isinstance(patch, dict):
+        return _py_deep_copy(patch)
+    out = dict(target) if isinstance(target, dict) else {}
+    for k, v in patch.items():
+        if v is None:
+            out.pop(k, None)
+        elif isinstance(v, dict):
+            out[k] = _py_merge_owned(out.get(k, {}), v)
+        else:
+            out[k] = _py_deep_copy(v)
+    return out
+
+
+def _py_merge_patch_owned(cur: dict, patch: dict) -> dict:
+    """Merge patch for a server that keeps the result: equal to
+    deep_copy(json_merge_patch(cur, patch)), but only what comes from the
+    caller's `patch` is copied. Every dict on the way to a patched key is
+    fresh, and every subtree of `cur` the patch does not touch is shared
+    (stored revisions are immutable, so sharing them is safe). The top-level
+    dict and `metadata` are always fresh: the server writes into both."""
+    out = _py_merge_owned(cur, patch)
+    if type(out) is dict and isinstance(cur, dict):
+        m = out.get("metadata")
+        if type(m) is dict and m is cur.get("metadata"):
+            out["metadata"] = dict(m)
+    return out
+
+
+# native fast path when built (see kube/objects.py: NATIVE_JSONTREE)
+if _native_jsontree is not None:
+    json_merge_patch = _native_jsontree.json_merge_patch
+    merge_patch_owned = _native_jsontree.merge_patch_owned
+else:
+    json_merge_patch = _py_json_merge_patch
+    merge_patch_owned = _py_merge_patch_owned

@@ -23,6 +23,12 @@ from __future__ import annotations
 import re
 from typing import Optional
 
+from .objects import _native_jsontree
+
+# verdict-only native walk (native/jsontree.cpp: crd_valid); None when the
+# extension is not built or GPU_PROVISIONER_PURE_PYTHON=1
+_native_valid = _native_jsontree.crd_valid if _native_jsontree is not None else None
+
 
 def _compile_schema(schema: dict, cache: Optional[dict] = None) -> dict:
     """One-time pass replacing `pattern` strings with compiled regexes
@@ -253,9 +259,21 @@ class CRDValidator:
         return cls(next(yaml.safe_load_all(open(path))))
 
     def __call__(self, new: dict, old: Optional[dict]) -> list:
-        errs: list = []
         if old is None:
             _apply_defaults(new, self.schema)
+        # native fast path: the same walk, answering only valid / not valid.
+        # Nearly every write is valid; for one that is not, the Python walk
+        # below runs as before and produces the violation strings.
+        if _native_valid is not None and _native_valid(
+            self.schema, new, old, self.spec_immutable
+        ):
+            return []
+        return self._violations(new, old)
+
+    def _violations(self, new: dict, old: Optional[dict]) -> list:
+        """The pure-Python validator (defaults already applied on create)."""
+        errs: list = []
+        if old is None:
             errs += validate(new, self.schema)
         else:
             # an unchanged subtree cannot become invalid — validate only

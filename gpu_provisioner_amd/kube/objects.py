@@ -9,6 +9,7 @@ behavioral spec.
 """
 from __future__ import annotations
 
+import os
 import re
 from dataclasses import dataclass
 from fractions import Fraction
@@ -389,7 +390,7 @@ def merge_taints(existing: Iterable[dict], desired: Iterable[dict]) -> list:
 # ---------------------------------------------------------------------------
 
 
-def deep_copy(obj):
+def _py_deep_copy(obj):
     """Fast deep copy for wire-format objects (pure JSON trees: dict/list/
     scalars). ~8× faster than copy.deepcopy, which dominated the provision
     path profile (49% of bench runtime) before this. Scalar leaves are
@@ -397,12 +398,27 @@ def deep_copy(obj):
     t = type(obj)
     if t is dict:
         return {
-            k: (deep_copy(v) if type(v) is dict or type(v) is list else v)
+            k: (_py_deep_copy(v) if type(v) is dict or type(v) is list else v)
             for k, v in obj.items()
         }
     if t is list:
-        return [deep_copy(v) if type(v) is dict or type(v) is list else v for v in obj]
+        return [_py_deep_copy(v) if type(v) is dict or type(v) is list else v for v in obj]
     return obj
+
+
+# The native JSON-tree extension (native/jsontree.cpp) replaces the tree
+# walks when it has been built; the Python bodies stay as the fallback and
+# as the reference the tests compare against. GPU_PROVISIONER_PURE_PYTHON=1
+# forces the fallback. NATIVE_JSONTREE tells which path is live.
+_native_jsontree = None
+if os.environ.get("GPU_PROVISIONER_PURE_PYTHON") != "1":
+    try:
+        from .._native import _jsontree as _native_jsontree  # type: ignore
+    except ImportError:
+        _native_jsontree = None
+NATIVE_JSONTREE = _native_jsontree is not None
+
+deep_copy = _native_jsontree.deep_copy if NATIVE_JSONTREE else _py_deep_copy
 
 
 def group_version_kind(obj: dict) -> tuple:
