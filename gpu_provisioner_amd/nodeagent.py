@@ -63,6 +63,29 @@ NO_BAD_WAVE = (1 << 64) - 1
 # comparable to GEMM benchmarks. 0 disables the floor.
 MIN_MFMA_SWEEP_TFLOPS = 1597.5
 
+# Single-wave MFMA checks: kind codes of nodeagent/mfma_frag.h. A kind yields
+# 256 32-bit words (1024 for the 32x32 tile), int32 for i8, float32 otherwise.
+MFMA_CHECK_KINDS = {
+    "f32_uniform": 0, "bf16_uniform": 1, "fp8_uniform": 2, "bf16_tile": 3, "f16_tile": 4,
+    "fp8_tile": 5, "i8_tile": 6, "bf16_tile32": 7, "mx_tile": 8, "mx_tile_x2": 9,
+}
+MFMA_CHECK_MAX_WORDS = 1024
+
+# check()'s boolean self-tests in order: (method, GPUReport field, problem label)
+_SELFTESTS = (
+    ("fma_selftest", "fma_ok", "VALU FMA selftest"),
+    ("mfma_selftest", "mfma_ok", "MFMA matrix-pipe selftest"),
+    ("mfma_bf16_selftest", "mfma_bf16_ok", "MFMA bf16 selftest"),
+    ("mfma_fp8_selftest", "mfma_fp8_ok", "MFMA fp8 selftest"),
+    ("mfma_bf16_tile_check", None, "MFMA bf16 tile check"),
+    ("mfma_fp8_tile_check", None, "MFMA fp8 tile check"),
+    ("mfma_i8_tile_check", None, "MFMA i8 tile check"),
+    ("mfma_f16_tile_check", None, "MFMA f16 tile check"),
+    ("mfma_mx_tile_check", None, "MFMA MX-scaled tile check"),
+    ("mfma_bf16_tile32_check", None, "MFMA 32x32 tile check"),
+    ("lds_selftest", "lds_ok", "LDS selftest"),
+)
+
 
 class NodeAgentError(RuntimeError):
     pass
@@ -315,6 +338,21 @@ class NodeAgent:
         semantics vs exact host references."""
         return self.lib.na_mfma_mx_tile_check(dev) == 0
 
+    def mfma_check_run(self, dev: int, kind: str):
+        """Launch the one wave of check ``kind`` (a key of ``MFMA_CHECK_KINDS``)
+        and return its raw words as a ctypes array of 1024 uint32, of which
+        the kind's first 256 (all 1024 for ``bf16_tile32``) are written."""
+        words = (ctypes.c_uint32 * MFMA_CHECK_MAX_WORDS)()
+        rc = self.lib.na_mfma_check_run(dev, MFMA_CHECK_KINDS[kind], words, len(words))
+        if rc != NA_OK:
+            raise NodeAgentError(f"mfma_check_run({dev}, {kind}): {self._err()}")
+        return words
+
+    def mfma_check_verify(self, kind: str, words) -> int:
+        """Compare a kind's words with the exact host reference (needs no GPU).
+        Returns the C code; on ``NA_ERR_VERIFY`` ``na_last_error`` names the word."""
+        return self.lib.na_mfma_check_verify(MFMA_CHECK_KINDS[kind], words, len(words))
+
     def lds_selftest(self, dev: int) -> tuple:
         """(ok, bytes_tested): whole-LDS pattern write/swizzled-read check."""
         tested = ctypes.c_longlong(0)
@@ -548,33 +586,14 @@ class NodeAgent:
                     g.problems.append(
                         f"HBM bandwidth {g.hbm_bw_gbs} GB/s below floor {MIN_HBM_BW_GBS}"
                     )
-                g.fma_ok = self.fma_selftest(d)
-                if not g.fma_ok:
-                    g.problems.append(f"VALU FMA selftest failed: {self._err()}")
-                g.mfma_ok = self.mfma_selftest(d)
-                if not g.mfma_ok:
-                    g.problems.append(f"MFMA matrix-pipe selftest failed: {self._err()}")
-                g.mfma_bf16_ok = self.mfma_bf16_selftest(d)
-                if not g.mfma_bf16_ok:
-                    g.problems.append(f"MFMA bf16 selftest failed: {self._err()}")
-                g.mfma_fp8_ok = self.mfma_fp8_selftest(d)
-                if not g.mfma_fp8_ok:
-                    g.problems.append(f"MFMA fp8 selftest failed: {self._err()}")
-                if not self.mfma_bf16_tile_check(d):
-                    g.problems.append(f"MFMA bf16 tile check failed: {self._err()}")
-                if not self.mfma_fp8_tile_check(d):
-                    g.problems.append(f"MFMA fp8 tile check failed: {self._err()}")
-                if not self.mfma_i8_tile_check(d):
-                    g.problems.append(f"MFMA i8 tile check failed: {self._err()}")
-                if not self.mfma_f16_tile_check(d):
-                    g.problems.append(f"MFMA f16 tile check failed: {self._err()}")
-                if not self.mfma_mx_tile_check(d):
-                    g.problems.append(f"MFMA MX-scaled tile check failed: {self._err()}")
-                if not self.mfma_bf16_tile32_check(d):
-                    g.problems.append(f"MFMA 32x32 tile check failed: {self._err()}")
-                g.lds_ok, g.lds_bytes_tested = self.lds_selftest(d)
-                if not g.lds_ok:
-                    g.problems.append(f"LDS selftest failed: {self._err()}")
+                for method, report_field, label in _SELFTESTS:
+                    ok = getattr(self, method)(d)
+                    if method == "lds_selftest":
+                        ok, g.lds_bytes_tested = ok
+                    if report_field:
+                        setattr(g, report_field, ok)
+                    if not ok:
+                        g.problems.append(f"{label} failed: {self._err()}")
                 g.sdma_bw_gbs = round(self.sdma_bandwidth(d), 1)
                 if g.sdma_bw_gbs < MIN_SDMA_BW_GBS:
                     g.problems.append(

@@ -6,10 +6,12 @@
 // validates the GPU stack end to end: device discovery (gfx950 arch, 288 GB
 // HBM3E), an HBM bandwidth self-test (float4 streaming copy; healthy nodes
 // reach ~6 TB/s of the 8 TB/s peak), an opt-in HBM data-integrity test
-// (pattern fill / verify+invert / verify, memtest.h), a VALU FMA correctness check, an MFMA
-// matrix-pipe check (v_mfma_f32_16x16x4_f32 — the CDNA4 matrix core the ML
-// workloads will live on), an opt-in chip-wide matrix-core sweep (one wave
-// per SIMD of every CU, mfmasweep.h), and the xGMI peer-to-peer link matrix.
+// (pattern fill / verify+invert / verify, memtest.h), a VALU FMA correctness
+// check, single-wave MFMA checks of every matrix-core datatype and geometry
+// the ML workloads live on (one kernel template over the operand traits of
+// mfma_frag.h, run and verified by na_mfma_check_run / _verify), an opt-in
+// chip-wide matrix-core sweep (one wave per SIMD of every CU, mfmasweep.h),
+// and the xGMI peer-to-peer link matrix.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
 // consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
@@ -21,9 +23,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "memtest.h"
+#include "mfma_frag.h"
 
 #define NA_OK 0
 #define NA_ERR_HIP -1
@@ -43,6 +47,44 @@
 static char na_last_error_buf[512];
 
 extern "C" const char* na_last_error() { return na_last_error_buf; }
+
+// ---------------------------------------------------------------------------
+// HIP resources: HIP_CHECK returns from the middle of a function, so whatever
+// an entry point allocates is held by one of these and released on every path
+// ---------------------------------------------------------------------------
+
+// n elements of device memory. `dev` >= 0 is made current before the free
+// (na_p2p_bandwidth holds a buffer on each of two devices).
+template <typename T>
+struct dev_buf {
+    T* p = nullptr;
+    int dev = -1;
+    dev_buf() = default;
+    explicit dev_buf(int d) : dev(d) {}
+    dev_buf(dev_buf&& o) noexcept : p(o.p), dev(o.dev) { o.p = nullptr; }
+    ~dev_buf() {
+        if (p == nullptr) return;
+        if (dev >= 0) (void)hipSetDevice(dev);
+        (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T)); }
+};
+
+template <int N>
+struct dev_events {
+    hipEvent_t e[N] = {};  // created by the caller, one HIP_CHECK each
+    ~dev_events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+struct dev_stream {
+    hipStream_t s = nullptr;
+    ~dev_stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -90,381 +132,80 @@ __global__ void fma_selftest_kernel(float* __restrict__ out, int iters) {
     out[blockIdx.x * blockDim.x + lane] = x;
 }
 
-// MFMA matrix-pipe self-test: one wave issues v_mfma_f32_16x16x4_f32 with
-// uniform operands. With A=alpha and B=beta everywhere and C=0, every output
-// element is K*alpha*beta (K=4) regardless of fragment layout, so the check
-// is layout-independent and still exercises the matrix pipe + AGPR file.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// Single-wave MFMA checks: one wave issues the MFMA of operand traits T
+// (mfma_frag.h) on the operands of generator GEN and stores its accumulator
+// registers as 32-bit words.
+//
+// uniform_operands: A = alpha = 1.5 and B = beta = 2.0 everywhere (exact in
+// f32, bf16 and E4M3: bytes 0x3C and 0x40), C = 0, two MFMAs so that
+// D = A*B + C chains through the accumulator. Every output element is
+// 2*K*alpha*beta regardless of fragment layout, so the check is
+// layout-independent and still exercises the input muxes, the matrix pipe
+// and the accumulator file. Register r of lane l goes to out[l*4 + r].
+//
+// tile_operands: D[MN x MN] = A[MN x K]·B[K x MN] from one MFMA on
+// ASYMMETRIC integer-valued data, stored row-major and checked against an
+// exact host reference; it fails if the per-lane fragment mapping is wrong
+// anywhere. Small integers keep both sides exact in every format and
+// summation order. k is taken modulo 64, which only the K = 128 MX kind
+// notices.
+__device__ __host__ inline int tile_a(int i, int k) { return (i * 31 + k * 7) % 7 - 3; }
+__device__ __host__ inline int tile_b(int k, int j) { return (k * 13 + j * 3) % 5 - 2; }
 
-__global__ void mfma_selftest_kernel(float* __restrict__ out, float alpha, float beta) {
-#if defined(__gfx950__)
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(alpha, beta, acc, 0, 0, 0);
-    // second accumulation: D = A*B + C must chain through the accumulator
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(alpha, beta, acc, 0, 0, 0);
-    int lane = threadIdx.x;
-    for (int i = 0; i < 4; ++i) out[lane * 4 + i] = acc[i];
-#else
-    out[threadIdx.x] = -1.0f;  // wrong arch: fail verification
-#endif
+__device__ inline void uniform_fill(float& a, float& b) { a = 1.5f, b = 2.0f; }
+__device__ inline void uniform_fill(bf16x8& a, bf16x8& b) {
+    for (int i = 0; i < 8; ++i) a[i] = (__bf16)1.5f, b[i] = (__bf16)2.0f;
+}
+__device__ inline void uniform_fill(long& a, long& b) {
+    a = 0x3C3C3C3C3C3C3C3CLL, b = 0x4040404040404040LL;
 }
 
-// MFMA datatype-path self-tests for the pipes ML workloads actually run on:
-// gfx950's 2xK bf16 form (v_mfma_f32_16x16x32_bf16, the CDNA4 training
-// workhorse) and the fp8 E4M3 form (v_mfma_f32_16x16x32_fp8_fp8, the serving
-// path). Same uniform-operand trick as the f32 test: with A=alpha and B=beta
-// everywhere and C=0, every output element is K*alpha*beta regardless of
-// fragment layout, so the check is layout-independent while still exercising
-// the low-precision input muxes and the accumulator file.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__global__ void mfma_bf16_selftest_kernel(float* __restrict__ out, float alpha, float beta) {
-#if defined(__gfx950__)
-    bf16x8 a, b;
-    for (int i = 0; i < 8; ++i) {
-        a[i] = (__bf16)alpha;
-        b[i] = (__bf16)beta;
+struct uniform_operands {
+    enum { UNIFORM = 1, CHAIN = 2 };
+    template <typename T>
+    static __device__ void fill(typename T::frag& a, typename T::frag& b, int) {
+        uniform_fill(a, b);
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-    int lane = threadIdx.x;
-    for (int i = 0; i < 4; ++i) out[lane * 4 + i] = acc[i];
-#else
-    out[threadIdx.x] = -1.0f;
-#endif
-}
-
-// fp8 operands are 8 packed E4M3 bytes per lane (one i64).
-__global__ void mfma_fp8_selftest_kernel(float* __restrict__ out, long a_bits, long b_bits) {
-#if defined(__gfx950__)
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a_bits, b_bits, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a_bits, b_bits, acc, 0, 0, 0);
-    int lane = threadIdx.x;
-    for (int i = 0; i < 4; ++i) out[lane * 4 + i] = acc[i];
-#else
-    out[threadIdx.x] = -1.0f;
-#endif
-}
-
-// Layout-correct bf16 GEMM tile: one v_mfma_f32_16x16x32_bf16 computing
-// D[16x16] = A[16x32]·B[32x16] with ASYMMETRIC integer-valued data, checked
-// against an exact host reference. The uniform-operand self-tests above are
-// layout-independent by construction; this one fails if the per-lane
-// fragment mapping (A: row=l&15, k=(l>>4)*8+i; B: col=l&15, same k;
-// D: col=l&15, row=(l>>4)*4+i) is wrong anywhere. Integer values keep both
-// sides exact regardless of summation order.
-__device__ __host__ inline float tile_a(int i, int k) { return (float)((i * 31 + k * 7) % 7 - 3); }
-__device__ __host__ inline float tile_b(int k, int j) { return (float)((k * 13 + j * 3) % 5 - 2); }
-
-__global__ void mfma_bf16_tile_kernel(float* __restrict__ out) {
-#if defined(__gfx950__)
-    int l = threadIdx.x;
-    bf16x8 a, b;
-    int arow = l & 15, kbase = (l >> 4) * 8;
-    for (int i = 0; i < 8; ++i) {
-        a[i] = (__bf16)tile_a(arow, kbase + i);
-        b[i] = (__bf16)tile_b(kbase + i, arow);  // B: col = l&15
+    template <typename T>
+    static __device__ int index(int l, int r) {
+        return l * 4 + r;
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-    int dcol = l & 15, drow0 = (l >> 4) * 4;
-    for (int i = 0; i < 4; ++i) out[(drow0 + i) * 16 + dcol] = acc[i];
-#else
-    out[threadIdx.x] = -1.0f;
-#endif
-}
+};
 
-extern "C" int na_mfma_bf16_tile_check(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, 256 * sizeof(float)));
-    mfma_bf16_tile_kernel<<<dim3(1), dim3(64)>>>(out);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[256];
-    HIP_CHECK(hipMemcpy(host, out, sizeof(host), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    for (int i = 0; i < 16; ++i) {
-        for (int j = 0; j < 16; ++j) {
-            float ref = 0.f;
-            for (int k = 0; k < 32; ++k) ref += tile_a(i, k) * tile_b(k, j);
-            if (host[i * 16 + j] != ref) {
-                std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                              "mfma bf16 tile: D[%d][%d] got %g want %g", i, j,
-                              host[i * 16 + j], ref);
-                return NA_ERR_VERIFY;
-            }
+struct tile_operands {
+    enum { UNIFORM = 0, CHAIN = 1 };
+    template <typename T>
+    static __device__ void fill(typename T::frag& a, typename T::frag& b, int l) {
+        const int rc = l % T::MN, k0 = (l / T::MN) * T::PER_LANE;
+#pragma unroll
+        for (int i = 0; i < T::PER_LANE; ++i) {
+            T::set(a, i, tile_a(rc, (k0 + i) % 64));
+            T::set(b, i, tile_b((k0 + i) % 64, rc));
         }
     }
-    return NA_OK;
-}
+    template <typename T>
+    static __device__ int index(int l, int r) {
+        return T::d_row(l, r) * T::MN + l % T::MN;
+    }
+};
 
-// f16 variant of the layout-correct tile (same fragment maps as bf16).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__global__ void mfma_f16_tile_kernel(float* __restrict__ out) {
+// out: T::MN * T::MN words. Launch with one wave (64 threads): MFMA is a
+// per-wave instruction. scale_a reaches the MX kind only.
+template <typename T, typename GEN>
+__global__ void mfma_check_kernel(void* __restrict__ out_, int scale_a) {
+    typename T::word* __restrict__ out = static_cast<typename T::word*>(out_);
 #if defined(__gfx950__)
-    int l = threadIdx.x;
-    int arow = l & 15, kbase = (l >> 4) * 8;
-    f16x8 a, b;
-    for (int i = 0; i < 8; ++i) {
-        a[i] = (_Float16)tile_a(arow, kbase + i);
-        b[i] = (_Float16)tile_b(kbase + i, arow);
-    }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
-    int dcol = l & 15, drow0 = (l >> 4) * 4;
-    for (int i = 0; i < 4; ++i) out[(drow0 + i) * 16 + dcol] = acc[i];
+    const int l = threadIdx.x;
+    typename T::frag a{}, b{};
+    GEN::template fill<T>(a, b, l);
+    typename T::acc acc{};
+    for (int n = 0; n < GEN::CHAIN; ++n) acc = T::mfma(a, b, acc, scale_a);
+#pragma unroll
+    for (int r = 0; r < (int)(sizeof(acc) / sizeof(typename T::word)); ++r)
+        out[GEN::template index<T>(l, r)] = acc[r];
 #else
-    out[threadIdx.x] = -1.0f;
+    out[threadIdx.x] = -1;  // wrong arch: fail verification
 #endif
-}
-
-extern "C" int na_mfma_f16_tile_check(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, 256 * sizeof(float)));
-    mfma_f16_tile_kernel<<<dim3(1), dim3(64)>>>(out);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[256];
-    HIP_CHECK(hipMemcpy(host, out, sizeof(host), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    for (int i = 0; i < 16; ++i) {
-        for (int j = 0; j < 16; ++j) {
-            float ref = 0.f;
-            for (int k = 0; k < 32; ++k) ref += tile_a(i, k) * tile_b(k, j);
-            if (host[i * 16 + j] != ref) {
-                std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                              "mfma f16 tile: D[%d][%d] got %g want %g", i, j,
-                              host[i * 16 + j], ref);
-                return NA_ERR_VERIFY;
-            }
-        }
-    }
-    return NA_OK;
-}
-
-// fp8 (E4M3) variant of the layout-correct tile: same fragment maps, the
-// 8 per-lane elements packed one byte each into the i64 operand (element i
-// at byte i). Values restricted to small integers exact in E4M3.
-__device__ __host__ inline int tile8_a(int i, int k) { return (i * 31 + k * 7) % 7 - 3; }
-__device__ __host__ inline int tile8_b(int k, int j) { return (k * 13 + j * 3) % 5 - 2; }
-
-__device__ __host__ inline unsigned char e4m3(int v) {
-    // encodings for -3..3 (sign | exp(bias 7) | 3-bit mantissa)
-    switch (v) {
-        case 0: return 0x00;
-        case 1: return 0x38;
-        case 2: return 0x40;
-        case 3: return 0x44;
-        case -1: return 0xB8;
-        case -2: return 0xC0;
-        default: return 0xC4;  // -3
-    }
-}
-
-__global__ void mfma_fp8_tile_kernel(float* __restrict__ out) {
-#if defined(__gfx950__)
-    int l = threadIdx.x;
-    int arow = l & 15, kbase = (l >> 4) * 8;
-    long a_bits = 0, b_bits = 0;
-    for (int i = 0; i < 8; ++i) {
-        a_bits |= (long)e4m3(tile8_a(arow, kbase + i)) << (8 * i);
-        b_bits |= (long)e4m3(tile8_b(kbase + i, arow)) << (8 * i);
-    }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a_bits, b_bits, acc, 0, 0, 0);
-    int dcol = l & 15, drow0 = (l >> 4) * 4;
-    for (int i = 0; i < 4; ++i) out[(drow0 + i) * 16 + dcol] = acc[i];
-#else
-    out[threadIdx.x] = -1.0f;
-#endif
-}
-
-extern "C" int na_mfma_fp8_tile_check(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, 256 * sizeof(float)));
-    mfma_fp8_tile_kernel<<<dim3(1), dim3(64)>>>(out);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[256];
-    HIP_CHECK(hipMemcpy(host, out, sizeof(host), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    for (int i = 0; i < 16; ++i) {
-        for (int j = 0; j < 16; ++j) {
-            float ref = 0.f;
-            for (int k = 0; k < 32; ++k) ref += (float)(tile8_a(i, k) * tile8_b(k, j));
-            if (host[i * 16 + j] != ref) {
-                std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                              "mfma fp8 tile: D[%d][%d] got %g want %g", i, j,
-                              host[i * 16 + j], ref);
-                return NA_ERR_VERIFY;
-            }
-        }
-    }
-    return NA_OK;
-}
-
-// i8 variant (v_mfma_i32_16x16x64_i8, K=64 — CDNA4's 2xK int8 path):
-// 16 per-lane elements packed 4-per-i32; k = (l>>4)*16 + i.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__global__ void mfma_i8_tile_kernel(int* __restrict__ out) {
-#if defined(__gfx950__)
-    int l = threadIdx.x;
-    int arow = l & 15, kbase = (l >> 4) * 16;
-    i32x4 a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
-    for (int i = 0; i < 16; ++i) {
-        unsigned char av = (unsigned char)(signed char)tile8_a(arow, kbase + i);
-        unsigned char bv = (unsigned char)(signed char)tile8_b(kbase + i, arow);
-        a[i / 4] |= (int)av << (8 * (i % 4));
-        b[i / 4] |= (int)bv << (8 * (i % 4));
-    }
-    i32x4 acc = {0, 0, 0, 0};
-    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc, 0, 0, 0);
-    int dcol = l & 15, drow0 = (l >> 4) * 4;
-    for (int i = 0; i < 4; ++i) out[(drow0 + i) * 16 + dcol] = acc[i];
-#else
-    out[threadIdx.x] = -1;
-#endif
-}
-
-extern "C" int na_mfma_i8_tile_check(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    int* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, 256 * sizeof(int)));
-    mfma_i8_tile_kernel<<<dim3(1), dim3(64)>>>(out);
-    HIP_CHECK(hipDeviceSynchronize());
-    int host[256];
-    HIP_CHECK(hipMemcpy(host, out, sizeof(host), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    for (int i = 0; i < 16; ++i) {
-        for (int j = 0; j < 16; ++j) {
-            int ref = 0;
-            for (int k = 0; k < 64; ++k) ref += tile8_a(i, k) * tile8_b(k, j);
-            if (host[i * 16 + j] != ref) {
-                std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                              "mfma i8 tile: D[%d][%d] got %d want %d", i, j,
-                              host[i * 16 + j], ref);
-                return NA_ERR_VERIFY;
-            }
-        }
-    }
-    return NA_OK;
-}
-
-// 32x32 geometry: v_mfma_f32_32x32x16_bf16 — same pipes, the OTHER tile
-// shape with its own fragment maps (A: row=l&31, k=(l>>5)*8+i; B: col
-// likewise; C/D per the ISA: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5),
-// 16 accumulator elements per lane).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__global__ void mfma_bf16_tile32_kernel(float* __restrict__ out) {
-#if defined(__gfx950__)
-    int l = threadIdx.x;
-    int arow = l & 31, kbase = (l >> 5) * 8;
-    bf16x8 a, b;
-    for (int i = 0; i < 8; ++i) {
-        a[i] = (__bf16)tile_a(arow, kbase + i);
-        b[i] = (__bf16)tile_b(kbase + i, arow);
-    }
-    f32x16 acc;
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-    int dcol = l & 31;
-    for (int r = 0; r < 16; ++r) {
-        int drow = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-        out[drow * 32 + dcol] = acc[r];
-    }
-#else
-    out[threadIdx.x] = -1.0f;
-#endif
-}
-
-extern "C" int na_mfma_bf16_tile32_check(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, 1024 * sizeof(float)));
-    mfma_bf16_tile32_kernel<<<dim3(1), dim3(64)>>>(out);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[1024];
-    HIP_CHECK(hipMemcpy(host, out, sizeof(host), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    for (int i = 0; i < 32; ++i) {
-        for (int j = 0; j < 32; ++j) {
-            float ref = 0.f;
-            for (int k = 0; k < 16; ++k) ref += tile_a(i, k) * tile_b(k, j);
-            if (host[i * 32 + j] != ref) {
-                std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                              "mfma bf16 32x32 tile: D[%d][%d] got %g want %g", i, j,
-                              host[i * 32 + j], ref);
-                return NA_ERR_VERIFY;
-            }
-        }
-    }
-    return NA_OK;
-}
-
-// Block-scaled MX path (gfx950-only): v_mfma_scale_f32_16x16x128_f8f6f4 —
-// the ONLY large-K low-precision MFMA and the fp4/fp6/MX serving pipe.
-// Two checks in one: (1) layout-correct asymmetric fp8-e4m3 data at
-// scale 1.0 against an exact host reference (per-lane A: row=l&15,
-// k=(l>>4)*32+i, byte i of <8 x i32>; B: col=l&15, same k; C/D as the
-// 16x16 family); (2) scale semantics — E8M0 exponent 128 on A doubles
-// the result.
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-__global__ void mfma_mx_tile_kernel(float* __restrict__ out, int scale_a) {
-#if defined(__gfx950__)
-    int l = threadIdx.x;
-    int arow = l & 15, kbase = (l >> 4) * 32;
-    i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 32; ++i) {
-        a[i / 4] |= (int)e4m3(tile8_a(arow, (kbase + i) % 64)) << (8 * (i % 4));
-        b[i / 4] |= (int)e4m3(tile8_b((kbase + i) % 64, arow)) << (8 * (i % 4));
-    }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int sb = 0x7F7F7F7F;  // E8M0 127 = 1.0 per block
-    int sa = scale_a * 0x01010101;
-    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-        a, b, acc, /*cbsz=*/0, /*blgp=*/0, /*opselA=*/0, sa, /*opselB=*/0, sb);
-    int dcol = l & 15, drow0 = (l >> 4) * 4;
-    for (int i = 0; i < 4; ++i) out[(drow0 + i) * 16 + dcol] = acc[i];
-#else
-    out[threadIdx.x] = -1.0f;
-#endif
-}
-
-extern "C" int na_mfma_mx_tile_check(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, 256 * sizeof(float)));
-    for (int pass = 0; pass < 2; ++pass) {
-        int scale_a = pass == 0 ? 0x7F : 0x80;  // 1.0, then 2.0
-        float mult = pass == 0 ? 1.0f : 2.0f;
-        mfma_mx_tile_kernel<<<dim3(1), dim3(64)>>>(out, scale_a);
-        HIP_CHECK(hipDeviceSynchronize());
-        float host[256];
-        HIP_CHECK(hipMemcpy(host, out, sizeof(host), hipMemcpyDeviceToHost));
-        for (int i = 0; i < 16; ++i) {
-            for (int j = 0; j < 16; ++j) {
-                float ref = 0.f;
-                for (int k = 0; k < 128; ++k)
-                    ref += (float)(tile8_a(i, k % 64) * tile8_b(k % 64, j));
-                ref *= mult;
-                if (host[i * 16 + j] != ref) {
-                    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                                  "mfma mx tile (scale %.0fx): D[%d][%d] got %g want %g",
-                                  mult, i, j, host[i * 16 + j], ref);
-                    (void)hipFree(out);
-                    return NA_ERR_VERIFY;
-                }
-            }
-        }
-    }
-    (void)hipFree(out);
-    return NA_OK;
 }
 
 // LDS self-test: fill the whole per-WG allocation with a position-dependent
@@ -510,127 +251,161 @@ extern "C" int na_device_info(int dev, char* name, int name_len, char* arch, int
 extern "C" int na_hbm_bandwidth(int dev, long long bytes, int iters, double* gbs) {
     HIP_CHECK(hipSetDevice(dev));
     size_t n = (size_t)bytes / sizeof(float4);
-    float4 *src = nullptr, *dst = nullptr;
-    HIP_CHECK(hipMalloc(&src, n * sizeof(float4)));
-    hipError_t e2 = hipMalloc(&dst, n * sizeof(float4));
+    dev_buf<float4> src, dst;
+    HIP_CHECK(src.alloc(n));
+    hipError_t e2 = dst.alloc(n);
     if (e2 != hipSuccess) {
-        (void)hipFree(src);
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s", hipGetErrorString(e2));
         return NA_ERR_HIP;
     }
-    HIP_CHECK(hipMemset(src, 1, n * sizeof(float4)));
+    HIP_CHECK(hipMemset(src.p, 1, n * sizeof(float4)));
     // sweep winner: 16384 WGs × 1024 threads, 4-deep in-chunk unroll
     dim3 grid(16384), block(1024);
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    copy_f4_kernel<<<grid, block>>>(src, dst, n);  // warmup
+    dev_events<2> t;
+    for (hipEvent_t& e : t.e) HIP_CHECK(hipEventCreate(&e));
+    copy_f4_kernel<<<grid, block>>>(src.p, dst.p, n);  // warmup
     HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipEventRecord(t0));
-    for (int i = 0; i < iters; ++i) copy_f4_kernel<<<grid, block>>>(src, dst, n);
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
+    HIP_CHECK(hipEventRecord(t.e[0]));
+    for (int i = 0; i < iters; ++i) copy_f4_kernel<<<grid, block>>>(src.p, dst.p, n);
+    HIP_CHECK(hipEventRecord(t.e[1]));
+    HIP_CHECK(hipEventSynchronize(t.e[1]));
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+    HIP_CHECK(hipEventElapsedTime(&ms, t.e[0], t.e[1]));
     // read + write
     *gbs = (2.0 * (double)bytes * iters) / (ms * 1e6);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    (void)hipFree(src);
-    (void)hipFree(dst);
     return NA_OK;
 }
 
 extern "C" int na_fma_selftest(int dev) {
     HIP_CHECK(hipSetDevice(dev));
     const int blocks = 1024, threads = 256, iters = 256;
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, (size_t)blocks * threads * sizeof(float)));
-    fma_selftest_kernel<<<dim3(blocks), dim3(threads)>>>(out, iters);
+    dev_buf<float> out;
+    HIP_CHECK(out.alloc((size_t)blocks * threads));
+    fma_selftest_kernel<<<dim3(blocks), dim3(threads)>>>(out.p, iters);
     HIP_CHECK(hipDeviceSynchronize());
-    float* host = new float[(size_t)blocks * threads];
-    HIP_CHECK(hipMemcpy(host, out, (size_t)blocks * threads * sizeof(float), hipMemcpyDeviceToHost));
-    int rc = NA_OK;
+    std::vector<float> host((size_t)blocks * threads);
+    HIP_CHECK(hipMemcpy(host.data(), out.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int i = 0; i < blocks * threads; ++i) {
         // fixpoint of x -> x/2 + 1/4 is 0.5; 256 iterations converge exactly
         if (host[i] != 0.5f) {
             std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
                           "fma selftest: lane %d got %g want 0.5", i, host[i]);
-            rc = NA_ERR_VERIFY;
-            break;
-        }
-    }
-    delete[] host;
-    (void)hipFree(out);
-    return rc;
-}
-
-extern "C" int na_mfma_selftest(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    const float alpha = 1.5f, beta = 2.0f;
-    const int n = 64 * 4;
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, n * sizeof(float)));
-    // one wave (64 threads): MFMA is a per-wave instruction
-    mfma_selftest_kernel<<<dim3(1), dim3(64)>>>(out, alpha, beta);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[n];
-    HIP_CHECK(hipMemcpy(host, out, n * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    // two chained MFMAs, K=4, uniform operands: every element = 2*K*alpha*beta
-    const float want = 2.0f * 4.0f * alpha * beta;
-    for (int i = 0; i < n; ++i) {
-        if (host[i] != want) {
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "mfma selftest: elem %d got %g want %g", i, host[i], want);
             return NA_ERR_VERIFY;
         }
     }
     return NA_OK;
 }
 
-// Shared verify for the 16x16x32 family: two chained MFMAs, K=32, uniform
-// operands → every element = 2*K*a*b.
-static int verify_mfma_out(const char* which, const float* host, int n, float want) {
-    for (int i = 0; i < n; ++i) {
-        if (host[i] != want) {
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "%s selftest: elem %d got %g want %g", which, i, host[i], want);
-            return NA_ERR_VERIFY;
+// One row per kind of the single-wave MFMA checks (mfma_frag.h), in the
+// order of the kind codes. `label` opens the failure message. D of the MX
+// kinds is `mult` times the unscaled product.
+struct mfma_check {
+    const char* label;
+    void (*kernel)(void*, int);
+    int mn, k, scale_a, mult;
+    bool uniform, is_int;
+    int words() const { return mn * mn; }  // 64 lanes x 4 registers for the uniform kinds too
+};
+
+template <typename T, typename GEN>
+static mfma_check mfma_check_row(const char* label, int scale_a = 0, int mult = 1) {
+    return {label, mfma_check_kernel<T, GEN>, T::MN, T::K, scale_a, mult, GEN::UNIFORM != 0,
+            std::is_same<typename T::word, int>::value};
+}
+
+static const mfma_check mfma_checks[NA_MFMA_KINDS] = {
+    mfma_check_row<mfma_f32_16x16x4, uniform_operands>("mfma selftest"),
+    mfma_check_row<mfma_bf16_16x16x32, uniform_operands>("mfma-bf16 selftest"),
+    mfma_check_row<mfma_fp8_16x16x32, uniform_operands>("mfma-fp8 selftest"),
+    mfma_check_row<mfma_bf16_16x16x32, tile_operands>("mfma bf16 tile"),
+    mfma_check_row<mfma_f16_16x16x32, tile_operands>("mfma f16 tile"),
+    mfma_check_row<mfma_fp8_16x16x32, tile_operands>("mfma fp8 tile"),
+    mfma_check_row<mfma_i8_16x16x64, tile_operands>("mfma i8 tile"),
+    mfma_check_row<mfma_bf16_32x32x16, tile_operands>("mfma bf16 32x32 tile"),
+    mfma_check_row<mfma_mx_16x16x128, tile_operands>("mfma mx tile (scale 1x)", 0x7F, 1),
+    mfma_check_row<mfma_mx_16x16x128, tile_operands>("mfma mx tile (scale 2x)", 0x80, 2),
+};
+
+static const mfma_check* mfma_check_args(const char* fn, int kind, const void* words,
+                                         int n_words) {
+    if (kind >= 0 && kind < NA_MFMA_KINDS && words != nullptr &&
+        n_words >= mfma_checks[kind].words())
+        return &mfma_checks[kind];
+    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                  "%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the "
+                  "32x32 tile (words %p, n_words %d)",
+                  fn, NA_MFMA_KINDS - 1, kind, words, n_words);
+    return nullptr;
+}
+
+// Launches the one wave of `kind` and copies its raw 32-bit words back:
+// int32 for the i8 kind, float32 otherwise. Argument errors are detected
+// before any HIP call.
+extern "C" int na_mfma_check_run(int dev, int kind, void* out, int n_words) {
+    const mfma_check* c = mfma_check_args("na_mfma_check_run", kind, out, n_words);
+    if (c == nullptr) return NA_ERR_ARG;
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<uint32_t> d;
+    HIP_CHECK(d.alloc((size_t)c->words()));
+    c->kernel<<<dim3(1), dim3(64)>>>(d.p, c->scale_a);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, d.p, (size_t)c->words() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NA_OK;
+}
+
+// Pure host code: compares the words of `kind` by value against the exact
+// reference, the constant 2*K*alpha*beta (alpha*beta = 3) for the uniform
+// kinds and the row-major integer product of the tile operands otherwise.
+// The first mismatch is named in na_last_error.
+extern "C" int na_mfma_check_verify(int kind, const void* words, int n_words) {
+    const mfma_check* c = mfma_check_args("na_mfma_check_verify", kind, words, n_words);
+    if (c == nullptr) return NA_ERR_ARG;
+    const float* f = static_cast<const float*>(words);
+    const int* w = static_cast<const int*>(words);
+    for (int e = 0; e < c->words(); ++e) {
+        const int i = e / c->mn, j = e % c->mn;
+        int want = 2 * c->k * 3;
+        if (!c->uniform) {
+            want = 0;
+            for (int k = 0; k < c->k; ++k) want += tile_a(i, k % 64) * tile_b(k % 64, j);
+            want *= c->mult;
         }
+        if (c->is_int ? w[e] == want : f[e] == (float)want) continue;
+        if (c->uniform)
+            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                          "%s: elem %d got %g want %g", c->label, e, f[e], (float)want);
+        else if (c->is_int)
+            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                          "%s: D[%d][%d] got %d want %d", c->label, i, j, w[e], want);
+        else
+            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                          "%s: D[%d][%d] got %g want %g", c->label, i, j, f[e], (float)want);
+        return NA_ERR_VERIFY;
     }
     return NA_OK;
 }
 
-extern "C" int na_mfma_bf16_selftest(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    // 1.5 and 2.0 are exact in bf16; 2*32*1.5*2.0 = 192 exact in f32
-    const float alpha = 1.5f, beta = 2.0f;
-    const int n = 64 * 4;
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, n * sizeof(float)));
-    mfma_bf16_selftest_kernel<<<dim3(1), dim3(64)>>>(out, alpha, beta);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[n];
-    HIP_CHECK(hipMemcpy(host, out, n * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    return verify_mfma_out("mfma-bf16", host, n, 2.0f * 32.0f * alpha * beta);
+static int mfma_check_one(int dev, int kind) {
+    uint32_t words[1024];
+    int rc = na_mfma_check_run(dev, kind, words, 1024);
+    return rc != NA_OK ? rc : na_mfma_check_verify(kind, words, 1024);
 }
 
-extern "C" int na_mfma_fp8_selftest(int dev) {
-    HIP_CHECK(hipSetDevice(dev));
-    // E4M3: 1.5 = 0x3C, 2.0 = 0x40 (both exact); 2*32*1.5*2.0 = 192
-    const long a_bits = 0x3C3C3C3C3C3C3C3CLL;
-    const long b_bits = 0x4040404040404040LL;
-    const int n = 64 * 4;
-    float* out = nullptr;
-    HIP_CHECK(hipMalloc(&out, n * sizeof(float)));
-    mfma_fp8_selftest_kernel<<<dim3(1), dim3(64)>>>(out, a_bits, b_bits);
-    HIP_CHECK(hipDeviceSynchronize());
-    float host[n];
-    HIP_CHECK(hipMemcpy(host, out, n * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(out);
-    return verify_mfma_out("mfma-fp8", host, n, 192.0f);
+extern "C" int na_mfma_selftest(int dev) { return mfma_check_one(dev, NA_MFMA_F32_UNIFORM); }
+extern "C" int na_mfma_bf16_selftest(int dev) { return mfma_check_one(dev, NA_MFMA_BF16_UNIFORM); }
+extern "C" int na_mfma_fp8_selftest(int dev) { return mfma_check_one(dev, NA_MFMA_FP8_UNIFORM); }
+extern "C" int na_mfma_bf16_tile_check(int dev) { return mfma_check_one(dev, NA_MFMA_BF16_TILE); }
+extern "C" int na_mfma_f16_tile_check(int dev) { return mfma_check_one(dev, NA_MFMA_F16_TILE); }
+extern "C" int na_mfma_fp8_tile_check(int dev) { return mfma_check_one(dev, NA_MFMA_FP8_TILE); }
+extern "C" int na_mfma_i8_tile_check(int dev) { return mfma_check_one(dev, NA_MFMA_I8_TILE); }
+extern "C" int na_mfma_bf16_tile32_check(int dev) {
+    return mfma_check_one(dev, NA_MFMA_BF16_TILE32);
+}
+// Two checks in one: layout at scale 1.0, then scale semantics — E8M0
+// exponent 128 on A doubles the result.
+extern "C" int na_mfma_mx_tile_check(int dev) {
+    int rc = mfma_check_one(dev, NA_MFMA_MX_TILE);
+    return rc != NA_OK ? rc : mfma_check_one(dev, NA_MFMA_MX_TILE_X2);
 }
 
 extern "C" int na_lds_selftest(int dev, long long* bytes_tested) {
@@ -642,23 +417,20 @@ extern "C" int na_lds_selftest(int dev, long long* bytes_tested) {
     size_t lds_bytes = prop.sharedMemPerBlock;
     if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
     size_t words = lds_bytes / sizeof(unsigned);
-    unsigned* fails = nullptr;
-    HIP_CHECK(hipMalloc(&fails, sizeof(unsigned)));
-    HIP_CHECK(hipMemset(fails, 0, sizeof(unsigned)));
+    dev_buf<unsigned> fails;
+    HIP_CHECK(fails.alloc(1));
+    HIP_CHECK(hipMemset(fails.p, 0, sizeof(unsigned)));
     // 2048 WGs: every CU's LDS array gets exercised multiple times
-    hipError_t e = hipSuccess;
-    lds_selftest_kernel<<<dim3(2048), dim3(256), lds_bytes>>>(fails, words);
-    e = hipGetLastError();
+    lds_selftest_kernel<<<dim3(2048), dim3(256), lds_bytes>>>(fails.p, words);
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        (void)hipFree(fails);
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "lds launch: %s",
                       hipGetErrorString(e));
         return NA_ERR_HIP;
     }
     HIP_CHECK(hipDeviceSynchronize());
     unsigned bad = 0;
-    HIP_CHECK(hipMemcpy(&bad, fails, sizeof(unsigned), hipMemcpyDeviceToHost));
-    (void)hipFree(fails);
+    HIP_CHECK(hipMemcpy(&bad, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (bytes_tested) *bytes_tested = (long long)lds_bytes;
     if (bad) {
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
@@ -674,35 +446,29 @@ extern "C" int na_sdma_bandwidth(int dev, long long bytes, int iters, double* gb
     // leans on for xGMI peer traffic. A sick SDMA engine shows up here
     // before any collective does.
     HIP_CHECK(hipSetDevice(dev));
-    void *src = nullptr, *dst = nullptr;
-    HIP_CHECK(hipMalloc(&src, (size_t)bytes));
-    hipError_t e2 = hipMalloc(&dst, (size_t)bytes);
+    dev_buf<char> src, dst;
+    HIP_CHECK(src.alloc((size_t)bytes));
+    hipError_t e2 = dst.alloc((size_t)bytes);
     if (e2 != hipSuccess) {
-        (void)hipFree(src);
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s", hipGetErrorString(e2));
         return NA_ERR_HIP;
     }
-    HIP_CHECK(hipMemset(src, 7, (size_t)bytes));
-    hipStream_t stream;
-    HIP_CHECK(hipStreamCreate(&stream));
-    HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, stream));  // warmup
-    HIP_CHECK(hipStreamSynchronize(stream));
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipEventRecord(t0, stream));
+    HIP_CHECK(hipMemset(src.p, 7, (size_t)bytes));
+    dev_stream stream;
+    HIP_CHECK(hipStreamCreate(&stream.s));
+    // warmup
+    HIP_CHECK(hipMemcpyAsync(dst.p, src.p, (size_t)bytes, hipMemcpyDeviceToDevice, stream.s));
+    HIP_CHECK(hipStreamSynchronize(stream.s));
+    dev_events<2> t;
+    for (hipEvent_t& e : t.e) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(t.e[0], stream.s));
     for (int i = 0; i < iters; ++i)
-        HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, stream));
-    HIP_CHECK(hipEventRecord(t1, stream));
-    HIP_CHECK(hipEventSynchronize(t1));
+        HIP_CHECK(hipMemcpyAsync(dst.p, src.p, (size_t)bytes, hipMemcpyDeviceToDevice, stream.s));
+    HIP_CHECK(hipEventRecord(t.e[1], stream.s));
+    HIP_CHECK(hipEventSynchronize(t.e[1]));
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+    HIP_CHECK(hipEventElapsedTime(&ms, t.e[0], t.e[1]));
     *gbs = (2.0 * (double)bytes * iters) / (ms * 1e6);  // read + write
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    (void)hipStreamDestroy(stream);
-    (void)hipFree(src);
-    (void)hipFree(dst);
     return NA_OK;
 }
 
@@ -721,39 +487,31 @@ extern "C" int na_p2p_matrix(int n, int* out /* n*n */) {
     return NA_OK;
 }
 
+// Returns with `src` current on every path once it has been made so: sbuf is
+// destroyed last, and each buffer is freed with its own device current.
 extern "C" int na_p2p_bandwidth(int src, int dst, long long bytes, int iters, double* gbs) {
     HIP_CHECK(hipSetDevice(src));
-    void* sbuf = nullptr;
-    HIP_CHECK(hipMalloc(&sbuf, (size_t)bytes));
+    dev_buf<char> sbuf(src), dbuf(dst);
+    HIP_CHECK(sbuf.alloc((size_t)bytes));
     HIP_CHECK(hipSetDevice(dst));
-    void* dbuf = nullptr;
-    hipError_t e = hipMalloc(&dbuf, (size_t)bytes);
+    hipError_t e = dbuf.alloc((size_t)bytes);
     if (e != hipSuccess) {
-        (void)hipSetDevice(src);
-        (void)hipFree(sbuf);
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s", hipGetErrorString(e));
         return NA_ERR_HIP;
     }
     HIP_CHECK(hipSetDevice(src));
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipMemcpyPeer(dbuf, dst, sbuf, src, (size_t)bytes));  // warmup
+    dev_events<2> t;
+    for (hipEvent_t& ev : t.e) HIP_CHECK(hipEventCreate(&ev));
+    HIP_CHECK(hipMemcpyPeer(dbuf.p, dst, sbuf.p, src, (size_t)bytes));  // warmup
     HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipEventRecord(t0));
+    HIP_CHECK(hipEventRecord(t.e[0]));
     for (int i = 0; i < iters; ++i)
-        HIP_CHECK(hipMemcpyPeer(dbuf, dst, sbuf, src, (size_t)bytes));
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
+        HIP_CHECK(hipMemcpyPeer(dbuf.p, dst, sbuf.p, src, (size_t)bytes));
+    HIP_CHECK(hipEventRecord(t.e[1]));
+    HIP_CHECK(hipEventSynchronize(t.e[1]));
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+    HIP_CHECK(hipEventElapsedTime(&ms, t.e[0], t.e[1]));
     *gbs = ((double)bytes * iters) / (ms * 1e6);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    (void)hipFree(sbuf);
-    (void)hipSetDevice(dst);
-    (void)hipFree(dbuf);
-    (void)hipSetDevice(src);
     return NA_OK;
 }
 
@@ -807,21 +565,18 @@ static int mt_launch(int mode, void* dptr, size_t nvec, mt_u64 v0, mt_u64 seed, 
     return NA_OK;
 }
 
-// Device-side accumulator, freed on every path.
+// Device-side accumulator.
 struct mt_dev_accum {
-    mt_accum* d = nullptr;
-    ~mt_dev_accum() {
-        if (d) (void)hipFree(d);
-    }
+    dev_buf<mt_accum> d;
     int init() {
-        HIP_CHECK(hipMalloc(&d, sizeof(mt_accum)));
+        HIP_CHECK(d.alloc(1));
         mt_accum zero = {0, UINT64_MAX, 0};
-        HIP_CHECK(hipMemcpy(d, &zero, sizeof(zero), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
         return NA_OK;
     }
     int read(uint64_t bytes, na_memtest_result* out) {
         mt_accum h;
-        HIP_CHECK(hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&h, d.p, sizeof(h), hipMemcpyDeviceToHost));
         out->bytes_tested = bytes;
         out->bad_words = h.bad_words;
         out->first_bad_offset = h.first_bad_offset;
@@ -881,25 +636,13 @@ extern "C" int na_memtest_verify(int dev, void* dptr, long long bytes, unsigned 
     rc = acc.init();
     if (rc != NA_OK) return rc;
     rc = mt_launch(flip ? MT_VERIFY_FLIP : MT_VERIFY, dptr, (size_t)bytes / 16, 0, seed, invert,
-                   acc.d);
+                   acc.d.p);
     if (rc != NA_OK) return rc;
     HIP_CHECK(hipDeviceSynchronize());
     rc = acc.read((uint64_t)bytes, out);
     if (rc != NA_OK) return rc;
     return mt_verdict(out);
 }
-
-// Everything na_hbm_memtest owns; the destructor frees it on every path.
-struct mt_region {
-    std::vector<void*> chunks;
-    std::vector<size_t> chunk_vecs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~mt_region() {
-        for (void* c : chunks) (void)hipFree(c);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
 
 // Whole test on a region the agent allocates itself, in chunks of at most
 // 1 GiB so no huge contiguous allocation is needed. pass_gbs (optional,
@@ -919,11 +662,12 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
     }
     HIP_CHECK(hipSetDevice(dev));
     const size_t nvec = (size_t)bytes / 16;
-    mt_region reg;
+    std::vector<dev_buf<mt_vec>> chunks;
+    std::vector<size_t> chunk_vecs;
     for (size_t off = 0; off < nvec; off += MT_MAX_LAUNCH_VECS) {
         size_t n = nvec - off < MT_MAX_LAUNCH_VECS ? nvec - off : MT_MAX_LAUNCH_VECS;
-        void* c = nullptr;
-        hipError_t e = hipMalloc(&c, n * 16);
+        chunks.emplace_back();
+        hipError_t e = chunks.back().alloc(n);
         if (e != hipSuccess) {
             (void)hipGetLastError();  // consumed here, not by a later check
             std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
@@ -931,13 +675,13 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
                           bytes, hipGetErrorString(e));
             return NA_ERR_HIP;
         }
-        reg.chunks.push_back(c);
-        reg.chunk_vecs.push_back(n);
+        chunk_vecs.push_back(n);
     }
     mt_dev_accum acc;
     int rc = acc.init();
     if (rc != NA_OK) return rc;
-    for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventCreate(&reg.ev[i]));
+    dev_events<4> ev;
+    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
 
     // each phase sweeps the WHOLE region before the next starts, so by the
     // time a chunk is read back the rest of the region has gone through the
@@ -946,21 +690,21 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
     static const int phase_invert[3] = {0, 0, 1};
     double phase_ms[3] = {0.0, 0.0, 0.0};
     for (int r = 0; r < rounds; ++r) {
-        HIP_CHECK(hipEventRecord(reg.ev[0]));
+        HIP_CHECK(hipEventRecord(ev.e[0]));
         for (int ph = 0; ph < 3; ++ph) {
             size_t off = 0;
-            for (size_t c = 0; c < reg.chunks.size(); ++c) {
-                rc = mt_launch(phase_mode[ph], reg.chunks[c], reg.chunk_vecs[c], off,
-                               seed + (mt_u64)r, phase_invert[ph], acc.d);
+            for (size_t c = 0; c < chunks.size(); ++c) {
+                rc = mt_launch(phase_mode[ph], chunks[c].p, chunk_vecs[c], off, seed + (mt_u64)r,
+                               phase_invert[ph], acc.d.p);
                 if (rc != NA_OK) return rc;
-                off += reg.chunk_vecs[c];
+                off += chunk_vecs[c];
             }
-            HIP_CHECK(hipEventRecord(reg.ev[ph + 1]));
+            HIP_CHECK(hipEventRecord(ev.e[ph + 1]));
         }
-        HIP_CHECK(hipEventSynchronize(reg.ev[3]));
+        HIP_CHECK(hipEventSynchronize(ev.e[3]));
         for (int ph = 0; ph < 3; ++ph) {
             float ms = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&ms, reg.ev[ph], reg.ev[ph + 1]));
+            HIP_CHECK(hipEventElapsedTime(&ms, ev.e[ph], ev.e[ph + 1]));
             phase_ms[ph] += ms;
         }
     }
@@ -1075,17 +819,6 @@ extern "C" int na_mfma_sweep_expected(unsigned long long seed, unsigned long lon
     return NA_OK;
 }
 
-// Everything a sweep launch owns; the destructor frees it on every path.
-struct ms_launch {
-    na_mfma_record* d = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~ms_launch() {
-        if (d) (void)hipFree(d);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 // One launch of `workgroups` x 4 waves, HIP-event timed; out receives the
 // 4 * workgroups records. Argument errors are detected before any HIP call.
 extern "C" int na_mfma_sweep_run(int dev, int dtype, int workgroups, int outer,
@@ -1110,24 +843,25 @@ extern "C" int na_mfma_sweep_run(int dev, int dtype, int workgroups, int outer,
     size_t lds_bytes = prop.sharedMemPerBlock;
     if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
     const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
-    ms_launch run;
-    HIP_CHECK(hipMalloc(&run.d, n * sizeof(na_mfma_record)));
+    dev_buf<na_mfma_record> d;
+    HIP_CHECK(d.alloc(n));
     // a record its wave never wrote carries no valid wave index and fails the verify
-    HIP_CHECK(hipMemset(run.d, 0xFF, n * sizeof(na_mfma_record)));
-    for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventCreate(&run.ev[i]));
+    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(na_mfma_record)));
+    dev_events<2> ev;
+    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
     const mt_u64 base = seed * MS_G;
     dim3 grid((unsigned)workgroups), block(MS_BLOCK);
-    HIP_CHECK(hipEventRecord(run.ev[0]));
+    HIP_CHECK(hipEventRecord(ev.e[0]));
     if (dtype == MS_BF16)
-        mfma_sweep_kernel<MS_BF16><<<grid, block, lds_bytes>>>(run.d, base, outer);
+        mfma_sweep_kernel<MS_BF16><<<grid, block, lds_bytes>>>(d.p, base, outer);
     else
-        mfma_sweep_kernel<MS_FP8><<<grid, block, lds_bytes>>>(run.d, base, outer);
+        mfma_sweep_kernel<MS_FP8><<<grid, block, lds_bytes>>>(d.p, base, outer);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(run.ev[1]));
-    HIP_CHECK(hipEventSynchronize(run.ev[1]));
+    HIP_CHECK(hipEventRecord(ev.e[1]));
+    HIP_CHECK(hipEventSynchronize(ev.e[1]));
     float elapsed = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&elapsed, run.ev[0], run.ev[1]));
-    HIP_CHECK(hipMemcpy(out, run.d, n * sizeof(na_mfma_record), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(na_mfma_record), hipMemcpyDeviceToHost));
     if (ms) *ms = (double)elapsed;
     return NA_OK;
 }

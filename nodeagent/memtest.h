@@ -1,5 +1,6 @@
 // HBM data-integrity kernels for the MI355X node agent (included from
-// agent.hip): pattern fill, verify, and fused verify-and-invert.
+// agent.hip, and from mfmasweep.h for mt_mix64): pattern fill, verify, and
+// fused verify-and-invert.
 //
 // Pattern (normative — tests/test_nodeagent_memtest.py carries an
 // independent numpy copy). The region is addressed in 16-byte vectors; v is

@@ -1,5 +1,6 @@
 // Chip-wide matrix-core sweep for the MI355X node agent (included from
-// agent.hip, after the MFMA vector typedefs and e4m3()).
+// agent.hip; operand packing and MFMA calls are mfma_frag.h's bf16 and fp8
+// 16x16x32 traits).
 //
 // The single-wave MFMA checks in agent.hip run on one SIMD of one CU. This
 // kernel puts one wave on every SIMD of every CU, has each run a long MFMA
@@ -18,8 +19,8 @@
 //   e   = mix64(seed*G + idx)
 //   A   = ((e >> 40) % 7) - 3          B = ((e >> 40) % 5) - 2
 //
-// Per-lane layout as in mfma_bf16_tile_kernel (A: row l&15, k = (l>>4)*8+i;
-// B: col l&15, same k; D: col l&15, row (l>>4)*4+i). Small integers are
+// Per-lane layout as in the single-wave tile checks (A: row l&15,
+// k = (l>>4)*8+i; B: col l&15, same k; D: col l&15, row (l>>4)*4+i). Small integers are
 // exact in bf16 and in E4M3, every partial sum is an exact f32 integer
 // (|D| <= 12288), so bf16 and fp8 give the same checksums in any order.
 //
@@ -33,8 +34,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "memtest.h"
+#include "mfma_frag.h"
 
 #define MS_BLOCK 256  // four waves: one per SIMD of the CU
 #define MS_WAVES_PER_WG (MS_BLOCK / 64)
@@ -65,46 +68,23 @@ __device__ __host__ inline int ms_value(mt_u64 base, mt_u64 w, int m, int t, int
 #if defined(__gfx950__)
 
 template <int DTYPE>
-struct ms_frag;
-template <>
-struct ms_frag<MS_BF16> {
-    typedef bf16x8 type;
-};
-template <>
-struct ms_frag<MS_FP8> {
-    typedef long type;  // 8 packed E4M3 bytes, element i at byte i
-};
-
-__device__ inline void ms_set(bf16x8& f, int i, int v) { f[i] = (__bf16)(float)v; }
-// e4m3()'s seven encodings packed into one constant (folded at compile
-// time), so the fragment set-up stays branch-free.
-__device__ inline void ms_set(long& f, int i, int v) {
-    mt_u64 table = 0;
-#pragma unroll
-    for (int x = -3; x <= 3; ++x) table |= (mt_u64)e4m3(x) << (8 * (x + 3));
-    f |= (long)((table >> (8 * (v + 3))) & 0xFF) << (8 * i);
-}
-
-__device__ inline f32x4 ms_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ inline f32x4 ms_mfma(long a, long b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
-}
+using ms_traits = typename std::conditional<DTYPE == MS_BF16, mfma_bf16_16x16x32,
+                                            mfma_fp8_16x16x32>::type;
 
 // One fold. The operands never change, so without the empty asm the
 // compiler may compute D once and drop the loop; "+v" tells it each A
 // fragment might have, at no instruction. One accumulation chain: this shape
 // issues back to back at the same ~16 cycles on 1, 4 or 16 accumulators, and
 // a single one leaves nothing to sum after the last MFMA.
-template <typename FRAG>
-__device__ inline f32x4 ms_fold(FRAG (&a)[MS_FRAGS], const FRAG (&b)[MS_FRAGS]) {
+template <typename T>
+__device__ inline f32x4 ms_fold(typename T::frag (&a)[MS_FRAGS],
+                                const typename T::frag (&b)[MS_FRAGS]) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ta = 0; ta < MS_FRAGS; ++ta) {
         asm volatile("" : "+v"(a[ta]));
 #pragma unroll
-        for (int tb = 0; tb < MS_FRAGS; ++tb) acc = ms_mfma(a[ta], b[tb], acc);
+        for (int tb = 0; tb < MS_FRAGS; ++tb) acc = T::mfma(a[ta], b[tb], acc);
     }
     return acc;
 }
@@ -128,7 +108,8 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
     // workgroup that holds more than half of a CU's LDS cannot share the CU
     // with a second one, so each of its four waves has a SIMD to itself —
     // the condition for back-to-back 16-cycle issue of this MFMA shape.
-    typedef typename ms_frag<DTYPE>::type frag;
+    typedef ms_traits<DTYPE> T;
+    typedef typename T::frag frag;
     const unsigned hw_id = __builtin_amdgcn_s_getreg(MS_GETREG(32, 0, 4));
     const unsigned xcc_id = __builtin_amdgcn_s_getreg(MS_GETREG(4, 0, 20));
     const int l = threadIdx.x & 63;
@@ -142,8 +123,8 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
         b[t] = frag{};
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            ms_set(a[t], i, ms_value(base, w, 0, t, r, k0 + i));
-            ms_set(b[t], i, ms_value(base, w, 1, t, r, k0 + i));
+            T::set(a[t], i, ms_value(base, w, 0, t, r, k0 + i));
+            T::set(b[t], i, ms_value(base, w, 1, t, r, k0 + i));
         }
     }
 
@@ -157,9 +138,9 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
     // Software-pipelined by one fold: the checksum update of fold j-1 does
     // not depend on fold j's MFMAs, so its VALU work issues in their shadow.
     mt_u64 c = 0;
-    f32x4 d = ms_fold(a, b);
+    f32x4 d = ms_fold<T>(a, b);
     for (int j = 1; j < outer; ++j) {
-        f32x4 dn = ms_fold(a, b);
+        f32x4 dn = ms_fold<T>(a, b);
         c = ms_update(c, d);
         d = dn;
     }

@@ -42,6 +42,8 @@ def test_hip_library_builds_and_loads():
         "na_mfma_f16_tile_check",
         "na_mfma_mx_tile_check",
         "na_mfma_bf16_tile32_check",
+        "na_mfma_check_run",
+        "na_mfma_check_verify",
         "na_p2p_matrix",
         "na_p2p_bandwidth",
         "na_last_error",
