@@ -15,13 +15,13 @@ AZURE_CLUSTER_NAME ?= gpu-provisioner-amd-aks
 AZURE_LOCATION ?= eastus2
 IDENTITY_NAME ?= gpu-provisioner-amd-id
 
-.PHONY: all build nodeagent jsontree unit-test gpu-test e2etests bench lint lint-full clean \
+.PHONY: all build nodeagent jsontree objmodel unit-test gpu-test e2etests bench lint lint-full clean \
         docker-build docker-build-multiarch helm-template \
         az-mkrg az-mkaks az-identity az-federated-credential az-patch-helm
 
 all: build
 
-build: nodeagent jsontree
+build: nodeagent jsontree objmodel
 
 nodeagent: gpu_provisioner_amd/_native/libmi355x_nodeagent.so
 
@@ -32,11 +32,17 @@ gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip nodeagen
 
 # CPython extension for the JSON-tree walks (deep copy, merge patch, CRD
 # validation verdict); the package falls back to pure Python without it
-JSONTREE_SO := gpu_provisioner_amd/_native/_jsontree$(shell $(PYTHON) -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
+# and for the object-model core (accessors, conditions, timestamps,
+# quantities, informer index store), built and bound the same way
+EXT_SUFFIX := $(shell $(PYTHON) -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
+JSONTREE_SO := gpu_provisioner_amd/_native/_jsontree$(EXT_SUFFIX)
+OBJMODEL_SO := gpu_provisioner_amd/_native/_objmodel$(EXT_SUFFIX)
 
 jsontree: $(JSONTREE_SO)
 
-$(JSONTREE_SO): native/jsontree.cpp
+objmodel: $(OBJMODEL_SO)
+
+gpu_provisioner_amd/_native/_%$(EXT_SUFFIX): native/%.cpp
 	mkdir -p gpu_provisioner_amd/_native
 	$(CXX) -O2 -std=c++17 -shared -fPIC \
 	  -I$$($(PYTHON) -c "import sysconfig; print(sysconfig.get_paths()['include'])") $< -o $@

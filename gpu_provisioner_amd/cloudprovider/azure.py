@@ -188,5 +188,5 @@ class AzureCloudProvider(CloudProvider):
         if "deleting" in (instance.state or "").lower():
             # surfacing in-flight deletion lets GC skip pools that are already
             # going away (reference cloudprovider.go:155-166)
-            ko.meta(nodeclaim)["deletionTimestamp"] = ko.fmt_time(ko.now())
+            ko.meta(nodeclaim)["deletionTimestamp"] = ko.now_rfc3339()
         return nodeclaim

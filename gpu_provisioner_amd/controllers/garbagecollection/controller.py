@@ -29,6 +29,7 @@ from ...events.recorder import EventRecorder
 from ...kube import objects as ko
 from ...kube.client import KubeClient, NotFoundError
 from ...kube.controller import Result, SingletonController
+from ...kube.informer import field_index
 
 log = logging.getLogger(__name__)
 
@@ -55,27 +56,16 @@ class InstanceGCController:
         self.adoption_age = adoption_age
         self.nodes = nodes
         if nodes is not None:
-            nodes.add_index(
-                "providerID", lambda o: o.get("spec", {}).get("providerID") or None
-            )
-            # same fn shape as InstanceProvider.set_nodes_informer — add_index
+            nodes.add_index("providerID", field_index(("spec", "providerID")))
+            # same paths as InstanceProvider.set_nodes_informer — add_index
             # is first-registration-wins by name, so both must index BOTH
             # agentpool label keys
             nodes.add_index(
                 "agentpool",
-                lambda o: [
-                    v
-                    for v in (
-                        (o.get("metadata", {}).get("labels") or {}).get(
-                            karpv1.AGENTPOOL_LABEL_KEY
-                        ),
-                        (o.get("metadata", {}).get("labels") or {}).get(
-                            karpv1.AZURE_AGENTPOOL_LABEL_KEY
-                        ),
-                    )
-                    if v
-                ]
-                or None,
+                field_index(
+                    ("metadata", "labels", karpv1.AGENTPOOL_LABEL_KEY),
+                    ("metadata", "labels", karpv1.AZURE_AGENTPOOL_LABEL_KEY),
+                ),
             )
         self.controller = SingletonController(self.NAME, self.reconcile, interval)
 
@@ -175,9 +165,7 @@ class NodeClaimGCController:
         if nodes is not None:
             # providerID index (the same one lifecycle registers) — a full
             # Node list per doomed claim is O(cluster) inside a loop
-            nodes.add_index(
-                "providerID", lambda o: o.get("spec", {}).get("providerID") or None
-            )
+            nodes.add_index("providerID", field_index(("spec", "providerID")))
         self.controller = SingletonController(self.NAME, self.reconcile, interval)
 
     async def reconcile(self, key: str) -> Optional[Result]:

@@ -26,7 +26,7 @@ from ...events.recorder import EventRecorder
 from ...kube import objects as ko
 from ...kube.client import KubeClient, NotFoundError
 from ...kube.controller import Controller, Result
-from ...kube.informer import Informer
+from ...kube.informer import Informer, field_index
 
 log = logging.getLogger(__name__)
 
@@ -51,9 +51,7 @@ class HealthController:
         if nodeclaims is not None:
             # same providerID index every other controller uses — an O(cluster)
             # NodeClaim list per unhealthy node does not belong on this path
-            nodeclaims.add_index(
-                "providerID", lambda o: o.get("status", {}).get("providerID") or None
-            )
+            nodeclaims.add_index("providerID", field_index(("status", "providerID")))
         self.controller = Controller(self.NAME, self.reconcile, workers=workers)
         self._first_seen: dict = {}  # (node, cond_type, status) -> first observed
         nodes.add_handler(self._on_node_event)

@@ -44,7 +44,7 @@ from ...events.recorder import EventRecorder
 from ...kube import objects as ko
 from ...kube.client import ConflictError, KubeClient, NotFoundError
 from ...kube.controller import Controller, Result, linear_scale_reconciles
-from ...kube.informer import Informer
+from ...kube.informer import Informer, field_index
 from ...metrics.registry import (
     INITIALIZATION_DURATION,
     LAUNCH_DURATION,
@@ -104,10 +104,8 @@ class LifecycleController:
             # asyncio workers are cheap coroutines so the same envelope applies
             workers=workers if workers is not None else linear_scale_reconciles(64, 1024),
         )
-        nodeclaims.add_index(
-            "providerID", lambda o: o.get("status", {}).get("providerID") or None
-        )
-        nodes.add_index("providerID", lambda o: o.get("spec", {}).get("providerID") or None)
+        nodeclaims.add_index("providerID", field_index(("status", "providerID")))
+        nodes.add_index("providerID", field_index(("spec", "providerID")))
         nodeclaims.add_handler(self._on_nodeclaim_event)
         nodes.add_handler(self._on_node_event)
 

@@ -23,7 +23,7 @@ from ...events.recorder import EventRecorder
 from ...kube import objects as ko
 from ...kube.client import ConflictError, KubeClient, NotFoundError
 from ...kube.controller import Controller, Result, linear_scale_reconciles
-from ...kube.informer import Informer
+from ...kube.informer import Informer, field_index
 from ...metrics.registry import (
     NODES_DRAINED,
     NODES_TERMINATED,
@@ -86,14 +86,10 @@ class TerminationController:
         # read-your-writes floor (see lifecycle): node-cache reads are
         # trusted only at-or-above our own last write's rv
         self._written_rv: OrderedDict = OrderedDict()
-        nodeclaims.add_index(
-            "providerID", lambda o: o.get("status", {}).get("providerID") or None
-        )
-        pods.add_index("nodeName", lambda o: o.get("spec", {}).get("nodeName") or None)
+        nodeclaims.add_index("providerID", field_index(("status", "providerID")))
+        pods.add_index("nodeName", field_index(("spec", "nodeName")))
         if volumeattachments is not None:
-            volumeattachments.add_index(
-                "nodeName", lambda o: o.get("spec", {}).get("nodeName") or None
-            )
+            volumeattachments.add_index("nodeName", field_index(("spec", "nodeName")))
         nodes.add_handler(self._on_node_event)
         # drain progress is event-driven: pod/volume-attachment changes on a
         # deleting node re-trigger its reconcile immediately, so the

@@ -9,7 +9,6 @@ from __future__ import annotations
 import asyncio
 import logging
 import time
-import uuid
 from collections import OrderedDict
 
 from ..kube import objects as ko
@@ -71,7 +70,8 @@ class EventRecorder:
             "apiVersion": "v1",
             "kind": "Event",
             "metadata": {
-                "name": f"{ko.name_of(obj)}.{uuid.uuid4().hex[:10]}",
+                # ten hex digits of a random uuid (its first group and a half)
+                "name": f"{ko.name_of(obj)}.{ko.uuid4_str().replace('-', '')[:10]}",
                 "namespace": self.namespace,
             },
             "involvedObject": {
@@ -85,8 +85,8 @@ class EventRecorder:
             "message": message,
             "type": event_type,
             "source": {"component": self.source},
-            "firstTimestamp": ko.fmt_time(ko.now()),
-            "lastTimestamp": ko.fmt_time(ko.now()),
+            "firstTimestamp": ko.now_rfc3339(),
+            "lastTimestamp": ko.now_rfc3339(),
             "count": 1,
         }
         try:

@@ -21,7 +21,6 @@ from __future__ import annotations
 import asyncio
 from collections import deque
 import itertools
-import uuid
 from collections import defaultdict
 from typing import Any, AsyncIterator, Callable, Optional
 
@@ -223,8 +222,8 @@ class InMemoryAPIServer:
                 raise AlreadyExistsError(f"{kind} {key[0]}/{key[1]} already exists")
             stored = ko.deep_copy(obj)
             m = ko.meta(stored)
-            m["uid"] = m.get("uid") or str(uuid.uuid4())
-            m["creationTimestamp"] = m.get("creationTimestamp") or ko.fmt_time(ko.now())
+            m["uid"] = m.get("uid") or ko.uuid4_str()
+            m["creationTimestamp"] = m.get("creationTimestamp") or ko.now_rfc3339()
             m["generation"] = 1
             self._validate(gvk, stored, None)  # CRD schema + defaults (422)
             self._bump(stored)
@@ -370,13 +369,13 @@ class InMemoryAPIServer:
             if ko.finalizers_of(cur):
                 if not ko.is_deleting(cur):
                     stored = {**cur, "metadata": {**cur["metadata"]}}
-                    ko.meta(stored)["deletionTimestamp"] = ko.fmt_time(ko.now())
+                    ko.meta(stored)["deletionTimestamp"] = ko.now_rfc3339()
                     self._bump(stored)
                     self._store[gvk][key] = stored
                     self._broadcast(gvk, MODIFIED, stored)
                 return
             stored = {**cur, "metadata": {**cur["metadata"]}}
-            ko.meta(stored)["deletionTimestamp"] = ko.fmt_time(ko.now())
+            ko.meta(stored)["deletionTimestamp"] = ko.now_rfc3339()
             self._bump(stored)
             del self._store[gvk][key]
             self._broadcast(gvk, DELETED, stored)
@@ -395,7 +394,7 @@ class InMemoryAPIServer:
             self.evictions.append(key)
             # eviction == graceful delete
             stored = ko.deep_copy(cur)
-            ko.meta(stored)["deletionTimestamp"] = ko.fmt_time(ko.now())
+            ko.meta(stored)["deletionTimestamp"] = ko.now_rfc3339()
             self._bump(stored)
             if ko.finalizers_of(cur):
                 self._store[gvk][key] = stored

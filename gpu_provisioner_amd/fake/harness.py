@@ -16,7 +16,7 @@ from ..apis import v1 as karpv1
 from ..cloudprovider.azure import AzureCloudProvider
 from ..cloudprovider.decorator import MetricsDecorator
 from ..events.recorder import EventRecorder
-from ..kube.informer import Informer, InformerFactory
+from ..kube.informer import Informer, InformerFactory, field_index
 from ..kube import objects as ko
 from ..providers.instance.provider import InstanceProvider
 from ..providers.instancetype.catalog import InstanceTypeProvider
@@ -102,7 +102,7 @@ class Harness:
         self.nodes: Informer = self.informers.informer("v1", "Node")
         self.instances.set_nodes_informer(self.nodes)
         self.pods: Informer = self.informers.informer("v1", "Pod")
-        self.pods.add_index("nodeName", lambda o: o.get("spec", {}).get("nodeName") or None)
+        self.pods.add_index("nodeName", field_index(("spec", "nodeName")))
         self.volumeattachments: Informer = self.informers.informer(
             "storage.k8s.io/v1", "VolumeAttachment"
         )

@@ -19,9 +19,87 @@ from .client import ADDED, BOOKMARK, DELETED, GoneError, KubeClient, MODIFIED
 log = logging.getLogger(__name__)
 
 
-def object_key(obj: dict) -> str:
-    ns = ko.namespace_of(obj)
-    return f"{ns}/{ko.name_of(obj)}" if ns else ko.name_of(obj)
+def _py_object_key(obj: dict) -> str:
+    ns = ko._py_namespace_of(obj)
+    return f"{ns}/{ko._py_name_of(obj)}" if ns else ko._py_name_of(obj)
+
+
+def _py_field_index(*paths) -> Callable:
+    """Index function over fixed key paths, e.g. ("spec", "providerID") or
+    the two ("metadata", "labels", <key>) paths of the agentpool index.
+    Follows add_index's contract: None for no value, otherwise the list of
+    non-empty values found at the paths, in path order. The top-level
+    section is read as obj.get(k, {}), deeper maps as .get(k) or {}. On an
+    object that breaks the wire format it does what the lambdas it replaced
+    did: a missing-but-not-absent section raises, and a single path whose
+    value is not a string gives that value itself for add_index to iterate."""
+    paths = tuple(tuple(p) for p in paths)
+
+    def index(obj: dict):
+        out = []
+        for path in paths:
+            cur = obj
+            for depth, k in enumerate(path[:-1]):
+                cur = cur.get(k, {}) if depth == 0 else (cur.get(k) or {})
+            v = cur.get(path[-1])
+            if v:
+                if len(paths) == 1 and not isinstance(v, str):
+                    return v
+                out.append(v)
+        return out or None
+
+    return index
+
+
+def _py_index_store(key: str, old: Optional[dict], new: Optional[dict], indexes: dict, cache: dict) -> None:
+    """Replace revision `old` of `key` by `new` in the index buckets and the
+    cache; either may be None (ADDED: no old, DELETED: no new)."""
+    for obj, remove in ((old, True), (new, False)):
+        if obj is None:
+            if not remove:
+                cache.pop(key, None)
+            continue
+        if not remove:
+            cache[key] = obj
+        for fn, idx in indexes.values():
+            vals = fn(obj)
+            if vals is None:
+                continue
+            if isinstance(vals, str):
+                vals = [vals]
+            for v in vals:
+                if remove:
+                    s = idx.get(v)
+                    if s is not None:
+                        s.discard(key)
+                        # drop emptied buckets: a defaultdict(set) keeps one
+                        # empty set per index value EVER seen, which is an
+                        # unbounded live-object leak at churn (measured
+                        # ~5 sets/claim, +260 MB RSS over a 20k-step soak)
+                        if not s:
+                            del idx[v]
+                else:
+                    idx[v].add(key)
+
+
+# native/objmodel.cpp replaces the three helpers above when it has been built
+# (ko.NATIVE_OBJMODEL). Its index_store runs every index function on both
+# revisions first and touches the buckets only where the values differ:
+# providerID, nodeName and the agentpool labels are write-once, so nearly
+# every MODIFIED event leaves the indexes alone.
+if ko.NATIVE_OBJMODEL:
+    ko._native_objmodel.set_fallbacks({"object_key": _py_object_key})
+    object_key = ko._native_objmodel.object_key
+    _index_store = ko._native_objmodel.index_store
+
+    def field_index(*paths) -> Callable:
+        return ko._native_objmodel.field_index(_py_field_index(*paths), *paths)
+
+else:
+    object_key = _py_object_key
+    _index_store = _py_index_store
+    field_index = _py_field_index
+field_index.__doc__ = _py_field_index.__doc__
 
 
 class Informer:
@@ -274,8 +352,8 @@ class Informer:
         # deletions that happened while we weren't watching
         for key in list(self._cache):
             if key not in new_keys:
-                gone = self._cache.pop(key)
-                self._reindex(key, gone, remove=True)
+                gone = self._cache[key]
+                _index_store(key, gone, None, self._indexes, self._cache)
                 self._notify(DELETED, gone)
         for obj in items:
             self._store(obj, event=MODIFIED if object_key(obj) in self._cache else ADDED)
@@ -289,41 +367,16 @@ class Informer:
                 continue  # rv advanced above; no object state change
             if event_type == DELETED:
                 key = object_key(obj)
-                old = self._cache.pop(key, None)
-                self._reindex(key, old or obj, remove=True)
+                old = self._cache.get(key)
+                _index_store(key, old or obj, None, self._indexes, self._cache)
                 self._notify(DELETED, obj)
             else:
                 self._store(obj, event=event_type)
 
     def _store(self, obj: dict, event: str) -> None:
         key = object_key(obj)
-        old = self._cache.get(key)
-        if old is not None:
-            self._reindex(key, old, remove=True)
-        self._cache[key] = obj
-        self._reindex(key, obj, remove=False)
+        _index_store(key, self._cache.get(key), obj, self._indexes, self._cache)
         self._notify(event, obj)
-
-    def _reindex(self, key: str, obj: dict, remove: bool) -> None:
-        for fn, idx in self._indexes.values():
-            vals = fn(obj)
-            if vals is None:
-                continue
-            if isinstance(vals, str):
-                vals = [vals]
-            for v in vals:
-                if remove:
-                    s = idx.get(v)
-                    if s is not None:
-                        s.discard(key)
-                        # drop emptied buckets: a defaultdict(set) keeps one
-                        # empty set per index value EVER seen, which is an
-                        # unbounded live-object leak at churn (measured
-                        # ~5 sets/claim, +260 MB RSS over a 20k-step soak)
-                        if not s:
-                            del idx[v]
-                else:
-                    idx[v].add(key)
 
     def _notify(self, event_type: str, obj: dict) -> None:
         for h in self._handlers:

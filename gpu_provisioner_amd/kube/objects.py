@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import os
 import re
+import uuid
 from dataclasses import dataclass
 from fractions import Fraction
 from datetime import datetime, timezone
@@ -25,13 +26,13 @@ def now() -> datetime:
     return datetime.now(timezone.utc)
 
 
-def fmt_time(t: datetime) -> str:
+def _py_fmt_time(t: datetime) -> str:
     t = t.astimezone(timezone.utc)
     # hand-rolled RFC3339: strftime was measurable on the provision path
     return f"{t.year:04d}-{t.month:02d}-{t.day:02d}T{t.hour:02d}:{t.minute:02d}:{t.second:02d}Z"
 
 
-def fmt_micro_time(t: datetime) -> str:
+def _py_fmt_micro_time(t: datetime) -> str:
     """metav1.MicroTime — Leases carry renew times at microsecond precision;
     whole-second truncation makes short leases look expired to followers."""
     t = t.astimezone(timezone.utc)
@@ -74,7 +75,7 @@ _SUFFIX = {
 }
 
 
-class Quantity:
+class _PyQuantity:
     """A kubernetes resource quantity. Immutable; compares by numeric value.
 
     Arithmetic is EXACT (Fraction, like upstream resource.Quantity's
@@ -84,7 +85,7 @@ class Quantity:
     __slots__ = ("raw", "value")
 
     def __init__(self, raw: "str | int | float | Fraction | Quantity"):
-        if isinstance(raw, Quantity):
+        if isinstance(raw, _PyQuantity):
             self.raw, self.value = raw.raw, raw.value
             return
         if isinstance(raw, Fraction):
@@ -111,7 +112,7 @@ class Quantity:
         return self.raw
 
     def __eq__(self, other: object) -> bool:
-        return isinstance(other, Quantity) and self.value == other.value
+        return isinstance(other, _PyQuantity) and self.value == other.value
 
     def __lt__(self, other: "Quantity") -> bool:
         return self.value < other.value
@@ -123,10 +124,10 @@ class Quantity:
         return hash(self.value)
 
     def __add__(self, other: "Quantity") -> "Quantity":
-        return Quantity(self.value + other.value)
+        return _PyQuantity(self.value + other.value)
 
     def __sub__(self, other: "Quantity") -> "Quantity":
-        return Quantity(self.value - other.value)
+        return _PyQuantity(self.value - other.value)
 
     def is_zero(self) -> bool:
         return self.value == 0
@@ -141,7 +142,86 @@ def _fmt_num(v: Fraction) -> str:
     return str(float(v))
 
 
-def qty(v: "str | int | float | Quantity") -> Quantity:
+class _NativeQuantity:
+    """Quantity with the same surface as the class above, kept as an exact
+    integer (numerator, denominator) pair in lowest terms. The native module
+    parses, adds, subtracts and formats on that pair; `value` builds the
+    Fraction only when it is read. Input the native parser does not cover
+    (and any value beyond 64 bits) takes the class above's route, so results
+    and error texts are its own."""
+
+    __slots__ = ("raw", "_num", "_den", "_frac")
+
+    def __init__(self, raw: "str | int | float | Fraction | Quantity"):
+        t = type(raw)
+        if t is str:
+            pair = _native_objmodel.qty_parse(raw)
+            if pair is not None:
+                self.raw = raw
+                self._num, self._den = pair
+                self._frac = None
+                return
+        elif t is int:
+            self.raw = str(raw)
+            self._num, self._den, self._frac = raw, 1, None
+            return
+        elif t is _NativeQuantity:
+            self.raw, self._num, self._den, self._frac = raw.raw, raw._num, raw._den, raw._frac
+            return
+        ref = _PyQuantity(raw)
+        self.raw = ref.raw
+        self._frac = v = ref.value
+        self._num, self._den = v.numerator, v.denominator
+
+    @classmethod
+    def _of(cls, num: int, den: int, raw: str) -> "_NativeQuantity":
+        q = cls.__new__(cls)
+        q._num, q._den, q.raw, q._frac = num, den, raw, None
+        return q
+
+    @property
+    def value(self) -> Fraction:
+        v = self._frac
+        if v is None:
+            v = self._frac = Fraction(self._num, self._den)
+        return v
+
+    def __repr__(self) -> str:
+        return f"Quantity({self.raw!r})"
+
+    def __str__(self) -> str:
+        return self.raw
+
+    def __eq__(self, other: object) -> bool:
+        return (
+            isinstance(other, _NativeQuantity)
+            and self._num == other._num
+            and self._den == other._den
+        )
+
+    def __lt__(self, other: "Quantity") -> bool:
+        return self._num * other._den < other._num * self._den
+
+    def __le__(self, other: "Quantity") -> bool:
+        return self._num * other._den <= other._num * self._den
+
+    def __hash__(self) -> int:
+        # hash(Fraction(n, 1)) == hash(n)
+        return hash(self._num) if self._den == 1 else hash(self.value)
+
+    def __add__(self, other: "Quantity") -> "Quantity":
+        r = _native_objmodel.qty_addsub(self._num, self._den, other._num, other._den, False)
+        return _NativeQuantity._of(*r) if r is not None else _NativeQuantity(self.value + other.value)
+
+    def __sub__(self, other: "Quantity") -> "Quantity":
+        r = _native_objmodel.qty_addsub(self._num, self._den, other._num, other._den, True)
+        return _NativeQuantity._of(*r) if r is not None else _NativeQuantity(self.value - other.value)
+
+    def is_zero(self) -> bool:
+        return self._num == 0
+
+
+def qty(v: "str | int | float | Quantity") -> "Quantity":
     return Quantity(v)
 
 
@@ -154,23 +234,23 @@ def meta(obj: dict) -> dict:
     return obj.setdefault("metadata", {})
 
 
-def name_of(obj: dict) -> str:
+def _py_name_of(obj: dict) -> str:
     return obj.get("metadata", {}).get("name", "")
 
 
-def namespace_of(obj: dict) -> str:
+def _py_namespace_of(obj: dict) -> str:
     return obj.get("metadata", {}).get("namespace", "")
 
 
-def uid_of(obj: dict) -> str:
+def _py_uid_of(obj: dict) -> str:
     return obj.get("metadata", {}).get("uid", "")
 
 
-def labels_of(obj: dict) -> dict:
+def _py_labels_of(obj: dict) -> dict:
     return obj.get("metadata", {}).get("labels") or {}
 
 
-def annotations_of(obj: dict) -> dict:
+def _py_annotations_of(obj: dict) -> dict:
     return obj.get("metadata", {}).get("annotations") or {}
 
 
@@ -182,12 +262,12 @@ def set_annotation(obj: dict, key: str, value: str) -> None:
     meta(obj).setdefault("annotations", {})[key] = value
 
 
-def finalizers_of(obj: dict) -> list:
+def _py_finalizers_of(obj: dict) -> list:
     return obj.get("metadata", {}).get("finalizers") or []
 
 
-def has_finalizer(obj: dict, fin: str) -> bool:
-    return fin in finalizers_of(obj)
+def _py_has_finalizer(obj: dict, fin: str) -> bool:
+    return fin in _py_finalizers_of(obj)
 
 
 def add_finalizer(obj: dict, fin: str) -> bool:
@@ -216,11 +296,11 @@ def creation_timestamp_of(obj: dict) -> Optional[datetime]:
     return parse_time(ts) if ts else None
 
 
-def is_deleting(obj: dict) -> bool:
+def _py_is_deleting(obj: dict) -> bool:
     return bool(obj.get("metadata", {}).get("deletionTimestamp"))
 
 
-def owner_references_of(obj: dict) -> list:
+def _py_owner_references_of(obj: dict) -> list:
     return obj.get("metadata", {}).get("ownerReferences") or []
 
 
@@ -248,23 +328,23 @@ CONDITION_FALSE = "False"
 CONDITION_UNKNOWN = "Unknown"
 
 
-def get_condition(obj: dict, cond_type: str) -> Optional[dict]:
+def _py_get_condition(obj: dict, cond_type: str) -> Optional[dict]:
     for c in obj.get("status", {}).get("conditions") or []:
         if c.get("type") == cond_type:
             return c
     return None
 
 
-def condition_is(obj: dict, cond_type: str, status: str) -> bool:
-    c = get_condition(obj, cond_type)
+def _py_condition_is(obj: dict, cond_type: str, status: str) -> bool:
+    c = _py_get_condition(obj, cond_type)
     return bool(c) and c.get("status") == status
 
 
-def condition_is_true(obj: dict, cond_type: str) -> bool:
-    return condition_is(obj, cond_type, CONDITION_TRUE)
+def _py_condition_is_true(obj: dict, cond_type: str) -> bool:
+    return _py_condition_is(obj, cond_type, CONDITION_TRUE)
 
 
-def set_condition(
+def _py_set_condition(
     obj: dict,
     cond_type: str,
     status: str,
@@ -283,7 +363,7 @@ def set_condition(
         if c.get("type") == cond_type:
             existing = c
             break
-    ts = fmt_time(at or now())
+    ts = _py_fmt_time(at or now())
     if existing is None:
         conds.append(
             {
@@ -316,14 +396,14 @@ def set_condition(
 # ---------------------------------------------------------------------------
 
 
-def node_is_ready(node: dict) -> bool:
+def _py_node_is_ready(node: dict) -> bool:
     for c in node.get("status", {}).get("conditions") or []:
         if c.get("type") == "Ready":
             return c.get("status") == CONDITION_TRUE
     return False
 
 
-def node_ready_condition(node: dict) -> Optional[dict]:
+def _py_node_ready_condition(node: dict) -> Optional[dict]:
     for c in node.get("status", {}).get("conditions") or []:
         if c.get("type") == "Ready":
             return c
@@ -342,7 +422,7 @@ def node_capacity(node: dict) -> dict:
     return node.get("status", {}).get("capacity") or {}
 
 
-def provider_id_of(node: dict) -> str:
+def _py_provider_id_of(node: dict) -> str:
     return node.get("spec", {}).get("providerID", "")
 
 
@@ -419,6 +499,59 @@ if os.environ.get("GPU_PROVISIONER_PURE_PYTHON") != "1":
 NATIVE_JSONTREE = _native_jsontree is not None
 
 deep_copy = _native_jsontree.deep_copy if NATIVE_JSONTREE else _py_deep_copy
+
+
+def _py_now_rfc3339() -> str:
+    """fmt_time(now()). The native version keeps the string of the current
+    second, so calls within one second return the same object."""
+    return _py_fmt_time(now())
+
+
+def _py_uuid4_str() -> str:
+    return str(uuid.uuid4())
+
+
+# The native object-model extension (native/objmodel.cpp) is bound the same
+# way: accessors, conditions, timestamps and quantities above keep their
+# Python bodies under _py_* names, and the public names point at whichever
+# path is live. NATIVE_OBJMODEL tells which. A native function hands any
+# input it does not mirror exactly (a non-dict where a dict is expected, a
+# datetime whose tzinfo is not timezone.utc) to the Python body of the same
+# name, which is why the bodies are registered with set_fallbacks.
+_native_objmodel = None
+if os.environ.get("GPU_PROVISIONER_PURE_PYTHON") != "1":
+    try:
+        from .._native import _objmodel as _native_objmodel  # type: ignore
+    except ImportError:
+        _native_objmodel = None
+NATIVE_OBJMODEL = _native_objmodel is not None
+
+_impl = _native_objmodel if NATIVE_OBJMODEL else None
+name_of = _impl.name_of if _impl else _py_name_of
+namespace_of = _impl.namespace_of if _impl else _py_namespace_of
+uid_of = _impl.uid_of if _impl else _py_uid_of
+labels_of = _impl.labels_of if _impl else _py_labels_of
+annotations_of = _impl.annotations_of if _impl else _py_annotations_of
+finalizers_of = _impl.finalizers_of if _impl else _py_finalizers_of
+has_finalizer = _impl.has_finalizer if _impl else _py_has_finalizer
+is_deleting = _impl.is_deleting if _impl else _py_is_deleting
+owner_references_of = _impl.owner_references_of if _impl else _py_owner_references_of
+provider_id_of = _impl.provider_id_of if _impl else _py_provider_id_of
+node_is_ready = _impl.node_is_ready if _impl else _py_node_is_ready
+node_ready_condition = _impl.node_ready_condition if _impl else _py_node_ready_condition
+get_condition = _impl.get_condition if _impl else _py_get_condition
+condition_is = _impl.condition_is if _impl else _py_condition_is
+condition_is_true = _impl.condition_is_true if _impl else _py_condition_is_true
+set_condition = _impl.set_condition if _impl else _py_set_condition
+fmt_time = _impl.fmt_time if _impl else _py_fmt_time
+fmt_micro_time = _impl.fmt_micro_time if _impl else _py_fmt_micro_time
+now_rfc3339 = _impl.now_rfc3339 if _impl else _py_now_rfc3339
+uuid4_str = _impl.uuid4_str if _impl else _py_uuid4_str
+Quantity = _NativeQuantity if _impl else _PyQuantity
+if _impl:
+    _impl.set_fallbacks(
+        {k[len("_py_"):]: v for k, v in list(globals().items()) if k.startswith("_py_") and callable(v)}
+    )
 
 
 def group_version_kind(obj: dict) -> tuple:

@@ -30,6 +30,7 @@ from ...cloudprovider.types import (
 )
 from ...kube import objects as ko
 from ...kube.client import KubeClient
+from ...kube.informer import field_index
 from ...utils.utils import parse_agent_pool_name_from_id
 from ..instancetype.catalog import InstanceTypeProvider
 from . import bootstrap
@@ -100,17 +101,10 @@ class InstanceProvider:
     def set_nodes_informer(self, informer) -> None:
         informer.add_index(
             "agentpool",
-            lambda o: [
-                v
-                for v in (
-                    (o.get("metadata", {}).get("labels") or {}).get(karpv1.AGENTPOOL_LABEL_KEY),
-                    (o.get("metadata", {}).get("labels") or {}).get(
-                        karpv1.AZURE_AGENTPOOL_LABEL_KEY
-                    ),
-                )
-                if v
-            ]
-            or None,
+            field_index(
+                ("metadata", "labels", karpv1.AGENTPOOL_LABEL_KEY),
+                ("metadata", "labels", karpv1.AZURE_AGENTPOOL_LABEL_KEY),
+            ),
         )
         self.nodes_informer = informer
 
