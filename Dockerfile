@@ -15,7 +15,7 @@ WORKDIR /src
 COPY nodeagent/ nodeagent/
 RUN hipcc --offload-arch=gfx950 -O3 -shared -fPIC \
       nodeagent/agent.hip -o /src/libmi355x_nodeagent.so
-# JSON-tree and object-model extensions: Ubuntu 22.04's python3 is 3.10, the runtime stage's
+# JSON-tree, object-model and revision-store extensions: Ubuntu 22.04's python3 is 3.10, the runtime stage's
 # version, so the modules' ABI tag matches (a mismatch is not loaded and the
 # package falls back to pure Python)
 COPY native/ native/
@@ -28,7 +28,11 @@ RUN apt-get update && apt-get install -y --no-install-recommends g++ python3-dev
     && c++ -O2 -std=c++17 -shared -fPIC \
       -I$(python3 -c "import sysconfig; print(sysconfig.get_paths()['include'])") \
       native/objmodel.cpp \
-      -o /src/_objmodel$(python3 -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
+      -o /src/_objmodel$(python3 -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))") \
+    && c++ -O2 -std=c++17 -shared -fPIC \
+      -I$(python3 -c "import sysconfig; print(sysconfig.get_paths()['include'])") \
+      native/revstore.cpp \
+      -o /src/_revstore$(python3 -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
 
 FROM python:3.10-slim AS runtime
 ARG VERSION=0.1.0
@@ -36,6 +40,6 @@ LABEL org.opencontainers.image.source=https://github.com/kaito-project/gpu-provi
 WORKDIR /app
 RUN pip install --no-cache-dir httpx prometheus_client uvicorn starlette pyyaml
 COPY gpu_provisioner_amd/ gpu_provisioner_amd/
-COPY --from=builder /src/libmi355x_nodeagent.so /src/_jsontree*.so /src/_objmodel*.so gpu_provisioner_amd/_native/
+COPY --from=builder /src/libmi355x_nodeagent.so /src/_jsontree*.so /src/_objmodel*.so /src/_revstore*.so gpu_provisioner_amd/_native/
 USER 65532:65532
 ENTRYPOINT ["python", "-m", "gpu_provisioner_amd"]

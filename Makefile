@@ -15,13 +15,13 @@ AZURE_CLUSTER_NAME ?= gpu-provisioner-amd-aks
 AZURE_LOCATION ?= eastus2
 IDENTITY_NAME ?= gpu-provisioner-amd-id
 
-.PHONY: all build nodeagent jsontree objmodel unit-test gpu-test e2etests bench lint lint-full clean \
+.PHONY: all build nodeagent jsontree objmodel revstore unit-test gpu-test e2etests bench lint lint-full clean \
         docker-build docker-build-multiarch helm-template \
         az-mkrg az-mkaks az-identity az-federated-credential az-patch-helm
 
 all: build
 
-build: nodeagent jsontree objmodel
+build: nodeagent jsontree objmodel revstore
 
 nodeagent: gpu_provisioner_amd/_native/libmi355x_nodeagent.so
 
@@ -33,14 +33,21 @@ gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip nodeagen
 # CPython extension for the JSON-tree walks (deep copy, merge patch, CRD
 # validation verdict); the package falls back to pure Python without it
 # and for the object-model core (accessors, conditions, timestamps,
-# quantities, informer index store), built and bound the same way
+# quantities, informer index store), built and bound the same way, and
+# for the in-memory apiserver's revision store (the verbs' success path)
 EXT_SUFFIX := $(shell $(PYTHON) -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
 JSONTREE_SO := gpu_provisioner_amd/_native/_jsontree$(EXT_SUFFIX)
 OBJMODEL_SO := gpu_provisioner_amd/_native/_objmodel$(EXT_SUFFIX)
+REVSTORE_SO := gpu_provisioner_amd/_native/_revstore$(EXT_SUFFIX)
 
 jsontree: $(JSONTREE_SO)
 
 objmodel: $(OBJMODEL_SO)
+
+revstore: $(REVSTORE_SO)
+
+# the copy and merge walks both of these include
+$(JSONTREE_SO) $(REVSTORE_SO): native/jsontree_walk.h
 
 gpu_provisioner_amd/_native/_%$(EXT_SUFFIX): native/%.cpp
 	mkdir -p gpu_provisioner_amd/_native

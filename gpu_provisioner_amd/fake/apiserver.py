@@ -19,8 +19,8 @@ simulated device plugin) can be tested fully in-process:
 from __future__ import annotations
 
 import asyncio
+import os
 from collections import deque
-import itertools
 from collections import defaultdict
 from typing import Any, AsyncIterator, Callable, Optional
 
@@ -44,6 +44,25 @@ from ..kube.client import (
 
 _WATCH_HISTORY = 4096  # events kept for resourceVersion resume
 _WATCH_BROKEN = "__WATCH_BROKEN__"  # sentinel: simulated dropped stream
+_EVENT_CAP = 20000  # Events kept; the oldest is dropped above this
+
+# The native revision store (native/revstore.cpp) runs the success path of
+# get/create/update/patch/delete in one call each, over the server's own
+# containers. On anything that would raise, and on input that is not plain
+# wire format, it returns NotImplemented with nothing touched, and the Python
+# body of the verb runs as before and produces the exception. The bodies stay
+# as that fallback and as the reference the tests compare against.
+# GPU_PROVISIONER_PURE_PYTHON=1 forces the fallback. NATIVE_REVSTORE tells
+# which path is live.
+_native_revstore = None
+if os.environ.get("GPU_PROVISIONER_PURE_PYTHON") != "1":
+    try:
+        from .._native import _revstore as _native_revstore  # type: ignore
+    except ImportError:
+        _native_revstore = None
+NATIVE_REVSTORE = _native_revstore is not None
+if NATIVE_REVSTORE:
+    _native_revstore.set_helpers(ko.uuid4_str, ko.now_rfc3339)
 
 # Field-selector support matrix of a real kube-apiserver. Every resource
 # accepts metadata.name/metadata.namespace; a handful register extra
@@ -115,7 +134,10 @@ class InMemoryAPIServer:
 
     def __init__(self):
         self._store: dict = defaultdict(dict)  # gvk -> {(ns,name): obj}
-        self._rv = itertools.count(1)
+        self._rv = 0  # last resourceVersion issued
+        # None: the Python bodies only (the tests' reference server)
+        self._native = _native_revstore
+        self._event_cap = _EVENT_CAP
         self._lock = asyncio.Lock()
         self._watchers: list = []  # (gvk, queue)
         # bounded ring: a list re-slice per event past the cap is an
@@ -135,7 +157,8 @@ class InMemoryAPIServer:
     # -- internals ----------------------------------------------------------
 
     def _next_rv(self) -> str:
-        return str(next(self._rv))
+        self._rv += 1
+        return str(self._rv)
 
     def _fire_reactors(self, verb: str, gvk: tuple, payload: Any) -> None:
         for r in list(self.reactors):
@@ -149,8 +172,8 @@ class InMemoryAPIServer:
         # Watch consumers (informers) treat event objects as read-only —
         # the client-go cache contract — and the server never mutates a
         # stored revision in place (every write replaces it).
-        rv = int(obj["metadata"]["resourceVersion"])
-        self._history.append((rv, gvk, event_type, obj))
+        # always called right after _bump(obj): the counter is obj's rv
+        self._history.append((self._rv, gvk, event_type, obj))
         for wgvk, queue in self._watchers:
             if wgvk == gvk:
                 queue.put_nowait((event_type, obj))
@@ -172,8 +195,13 @@ class InMemoryAPIServer:
 
     async def get(self, api_version: str, kind: str, name: str, namespace: str) -> dict:
         async with self._lock:
-            gvk = _gvk(api_version, kind)
-            self._fire_reactors("get", gvk, name)
+            gvk = (api_version, kind)
+            if self.reactors:
+                self._fire_reactors("get", gvk, name)
+            if self._native is not None:
+                out = self._native.get(self._store[gvk], namespace, name)
+                if out is not NotImplemented:
+                    return out
             obj = self._store[gvk].get(_key(namespace, name))
             if obj is None:
                 raise NotFoundError(f"{kind} {namespace}/{name} not found")
@@ -205,18 +233,22 @@ class InMemoryAPIServer:
             return out, str(self._peek_rv())
 
     def _peek_rv(self) -> int:
-        # itertools.count has no peek; track via history / probe
-        c = next(self._rv)
-        self._rv = itertools.chain([c], self._rv)  # push back
-        return c - 1
+        return self._rv
 
     async def create(self, obj: dict) -> dict:
         async with self._lock:
             api_version, kind = obj.get("apiVersion", ""), obj.get("kind", "")
             if not api_version or not kind or not ko.name_of(obj):
                 raise InvalidError("apiVersion, kind and metadata.name are required")
-            gvk = _gvk(api_version, kind)
-            self._fire_reactors("create", gvk, obj)
+            gvk = (api_version, kind)
+            if self.reactors:
+                self._fire_reactors("create", gvk, obj)
+            if self._native is not None:
+                out = self._native.create(
+                    self, gvk, self._store[gvk], obj, self.validators.get(gvk), self._event_cap
+                )
+                if out is not NotImplemented:
+                    return out
             key = _key(ko.namespace_of(obj), ko.name_of(obj))
             if key in self._store[gvk]:
                 raise AlreadyExistsError(f"{kind} {key[0]}/{key[1]} already exists")
@@ -230,7 +262,7 @@ class InMemoryAPIServer:
             self._store[gvk][key] = stored
             # Events are capped like a real cluster's event TTL would bound
             # them — long soaks otherwise grow the store without limit
-            if kind == "Event" and len(self._store[gvk]) > 20000:
+            if kind == "Event" and len(self._store[gvk]) > self._event_cap:
                 drop = next(iter(self._store[gvk]))
                 del self._store[gvk][drop]
             self._broadcast(gvk, ADDED, stored)
@@ -239,8 +271,15 @@ class InMemoryAPIServer:
     async def update(self, obj: dict, subresource: str = "") -> dict:
         async with self._lock:
             api_version, kind = obj.get("apiVersion", ""), obj.get("kind", "")
-            gvk = _gvk(api_version, kind)
-            self._fire_reactors("update", gvk, obj)
+            gvk = (api_version, kind)
+            if self.reactors:
+                self._fire_reactors("update", gvk, obj)
+            if self._native is not None:
+                out = self._native.update(
+                    self, gvk, self._store[gvk], obj, subresource, self.validators.get(gvk)
+                )
+                if out is not NotImplemented:
+                    return out
             key = _key(ko.namespace_of(obj), ko.name_of(obj))
             cur = self._store[gvk].get(key)
             if cur is None:
@@ -324,8 +363,16 @@ class InMemoryAPIServer:
         subresource: str,
     ) -> dict:
         async with self._lock:
-            gvk = _gvk(api_version, kind)
-            self._fire_reactors("patch", gvk, name)
+            gvk = (api_version, kind)
+            if self.reactors:
+                self._fire_reactors("patch", gvk, name)
+            if self._native is not None:
+                out = self._native.patch(
+                    self, gvk, self._store[gvk], namespace, name, patch, subresource,
+                    self.validators.get(gvk),
+                )
+                if out is not NotImplemented:
+                    return out
             key = _key(namespace, name)
             cur = self._store[gvk].get(key)
             if cur is None:
@@ -358,8 +405,15 @@ class InMemoryAPIServer:
         grace_period_seconds: Optional[int] = None,
     ) -> None:
         async with self._lock:
-            gvk = _gvk(api_version, kind)
-            self._fire_reactors("delete", gvk, name)
+            gvk = (api_version, kind)
+            if self.reactors:
+                self._fire_reactors("delete", gvk, name)
+            if self._native is not None:
+                out = self._native.delete(
+                    self, gvk, self._store[gvk], namespace, name, uid_precondition
+                )
+                if out is not NotImplemented:
+                    return out
             key = _key(namespace, name)
             cur = self._store[gvk].get(key)
             if cur is None:
