@@ -6,7 +6,7 @@ evidence. Fails LOUDLY if the native library is missing on a GPU machine —
 there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
-[--memtest-bytes N] [--mfma-sweep]``
+[--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -70,6 +70,28 @@ MFMA_CHECK_KINDS = {
     "fp8_tile": 5, "i8_tile": 6, "bf16_tile32": 7, "mx_tile": 8, "mx_tile_x2": 9,
 }
 MFMA_CHECK_MAX_WORDS = 1024
+
+# Single-wave MX checks (the block-scaled f8f6f4 instructions in every operand
+# format): kind codes NA_MX_* of nodeagent/mfma_frag.h. A kind yields 256
+# float32 words (1024 for the 32x32 tile).
+MX_CHECK_KINDS = {
+    "fp4": 0, "fp6": 1, "bf6": 2, "bf8": 3, "fp8_fp4": 4, "fp4_32": 5,
+    "fp4_codes": 6, "fp6_codes": 7, "bf6_codes": 8,
+}
+# OCP MX element formats, coded as the instruction's cbsz / blgp
+# (nodeagent/mx_formats.h), and their element widths in bits.
+MX_FORMATS = {"e4m3": 0, "e5m2": 1, "e2m3": 2, "e3m2": 3, "e2m1": 4}
+MX_FORMAT_BITS = {"e4m3": 8, "e5m2": 8, "e2m3": 6, "e3m2": 6, "e2m1": 4}
+
+# Chip-wide MX sweep: the matrix-core sweep on the block-scaled 16x16x128
+# instruction. The default seed is "MI355XMX".
+DEFAULT_MX_SWEEP_SEED = 0x4D493335_35584D58
+MX_SWEEP_FORMATS = {"fp4": 0, "fp6": 1}
+# fp4 floor of the default MX sweep: 0.70 x the 7672.1 TFLOP/s median of five
+# processes on MI355X (profiles/mx_sweep_mi355x.txt), the rule of the bf16
+# floor above and with its caveat: not comparable to GEMM benchmarks.
+# 0 disables the floor.
+MIN_MX_SWEEP_TFLOPS = 5370.5
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -247,6 +269,12 @@ class GPUReport:
     mfma_sweep_clock_mhz: float = 0.0  # bf16 run; informational, no floor
     mfma_sweep_units_seen: int = 0
     mfma_sweep_bad_waves: int = 0
+    # single-wave MX checks and chip-wide MX sweep (opt-in; "not run" by default)
+    mx_checks_run: int = 0  # kinds run
+    mx_checks_failed: list = field(default_factory=list)  # names of the kinds that failed
+    mx_sweep_fp4_tflops: float = 0.0
+    mx_sweep_fp6_tflops: float = 0.0
+    mx_sweep_bad_waves: int = 0
 
 
 @dataclass
@@ -333,9 +361,11 @@ class NodeAgent:
         return self.lib.na_mfma_bf16_tile32_check(dev) == 0
 
     def mfma_mx_tile_check(self, dev: int) -> bool:
-        """Block-scaled MX path (v_mfma_scale_f32_16x16x128_f8f6f4, the
-        fp4/fp6/MX serving pipe): layout-correct fp8 data + E8M0 scale
-        semantics vs exact host references."""
+        """Block-scaled MX path (v_mfma_scale_f32_16x16x128_f8f6f4) on E4M3
+        operands only, with one scale for all of A (1.0, then 2.0) and B's
+        at 1.0, vs exact host references. The other operand formats (fp4,
+        fp6, bf6, bf8), per-lane scales and the scale byte select are
+        covered by ``mx_checks``."""
         return self.lib.na_mfma_mx_tile_check(dev) == 0
 
     def mfma_check_run(self, dev: int, kind: str):
@@ -352,6 +382,57 @@ class NodeAgent:
         """Compare a kind's words with the exact host reference (needs no GPU).
         Returns the C code; on ``NA_ERR_VERIFY`` ``na_last_error`` names the word."""
         return self.lib.na_mfma_check_verify(MFMA_CHECK_KINDS[kind], words, len(words))
+
+    # -- single-wave MX checks ------------------------------------------------
+
+    def mx_decode(self, fmt: str, code: int) -> float:
+        """Value of ``code`` in format ``fmt`` (a key of ``MX_FORMATS``), by
+        the decoder the host references use (needs no GPU)."""
+        out = ctypes.c_float(0)
+        if self.lib.na_mx_decode(MX_FORMATS[fmt], code, ctypes.byref(out)) != NA_OK:
+            raise NodeAgentError(f"mx_decode({fmt}, {code}): {self._err()}")
+        return out.value
+
+    def mx_pack(self, fmt: str, codes) -> list:
+        """``codes`` (a multiple of 32 of them) packed the way the kernels
+        pack a lane's fragments: element i of a fragment at bit i * width,
+        little-endian across 32-bit words (needs no GPU)."""
+        n = len(codes)
+        words = (ctypes.c_uint32 * max(n * MX_FORMAT_BITS[fmt] // 32, 1))()
+        rc = self.lib.na_mx_pack(MX_FORMATS[fmt], (ctypes.c_int * max(n, 1))(*codes), n, words,
+                                 len(words))
+        if rc != NA_OK:
+            raise NodeAgentError(f"mx_pack({fmt}): {self._err()}")
+        return list(words)
+
+    def mx_check_run(self, dev: int, kind: str):
+        """Launch the one wave of MX check ``kind`` (a key of
+        ``MX_CHECK_KINDS``) and return its raw words as a ctypes array of
+        1024 uint32, of which the kind's first 256 (all 1024 for ``fp4_32``)
+        are written: float32 bit patterns."""
+        words = (ctypes.c_uint32 * MFMA_CHECK_MAX_WORDS)()
+        rc = self.lib.na_mx_check_run(dev, MX_CHECK_KINDS[kind], words, len(words))
+        if rc != NA_OK:
+            raise NodeAgentError(f"mx_check_run({dev}, {kind}): {self._err()}")
+        return words
+
+    def mx_check_verify(self, kind: str, words) -> int:
+        """Compare a kind's words with the exact host reference (needs no GPU).
+        Returns the C code; on ``NA_ERR_VERIFY`` ``na_last_error`` names the word."""
+        return self.lib.na_mx_check_verify(MX_CHECK_KINDS[kind], words, len(words))
+
+    def mx_checks(self, dev: int) -> bool:
+        """Every kind of ``MX_CHECK_KINDS`` in turn, one wave each, stopping at
+        the first that fails (``na_last_error`` names its first wrong word)."""
+        return self.lib.na_mx_checks(dev) == NA_OK
+
+    def _run_mx_checks(self, g: GPUReport) -> None:
+        for kind in MX_CHECK_KINDS:  # all of them: each failure names its own word
+            words = self.mx_check_run(g.index, kind)
+            g.mx_checks_run += 1
+            if self.mx_check_verify(kind, words) != NA_OK:
+                g.mx_checks_failed.append(kind)
+                g.problems.append(f"MX check {kind} failed: {self._err()}")
 
     def lds_selftest(self, dev: int) -> tuple:
         """(ok, bytes_tested): whole-LDS pattern write/swizzled-read check."""
@@ -537,6 +618,81 @@ class NodeAgent:
             if not res.ok:
                 g.problems.append(f"MFMA sweep {dtype}: {res.describe()}")
 
+    # -- chip-wide MX sweep ------------------------------------------------------
+
+    @staticmethod
+    def _mx_format(fmt: str) -> int:
+        if fmt not in MX_SWEEP_FORMATS:
+            raise NodeAgentError(f"mx sweep: format {fmt!r} is not one of fp4, fp6")
+        return MX_SWEEP_FORMATS[fmt]
+
+    def mx_sweep_expected(self, wave: int, outer: int, seed: int = DEFAULT_MX_SWEEP_SEED) -> int:
+        """Checksum wave ``wave`` of the MX sweep must report after ``outer``
+        folds, in either format (host arithmetic only; needs no GPU)."""
+        out = ctypes.c_uint64(0)
+        rc = self.lib.na_mx_sweep_expected(
+            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"mx_sweep_expected: {self._err()}")
+        return out.value
+
+    def mx_sweep_run(self, dev: int, fmt: str = "fp4", workgroups: int = 1, outer: int = 1,
+                     seed: int = DEFAULT_MX_SWEEP_SEED) -> tuple:
+        """As ``mfma_sweep_run``, on v_mfma_scale_f32_16x16x128_f8f6f4 with
+        operands in ``fmt`` ("fp4" = E2M1, "fp6" = E2M3) and scales of 1.0."""
+        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
+        recs = (MfmaRecord * max(n, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_mx_sweep_run(
+            dev, self._mx_format(fmt), workgroups, outer, ctypes.c_ulonglong(seed),
+            recs, ctypes.c_longlong(n), ctypes.byref(ms),
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"mx_sweep_run({dev}): {self._err()}")
+        return recs, ms.value
+
+    def mx_sweep_verify(self, recs, outer: int, seed: int = DEFAULT_MX_SWEEP_SEED,
+                        fmt: str = "fp4") -> tuple:
+        """As ``mfma_sweep_verify``, against the MX sweep's reference."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_mx_sweep_verify(
+            recs, ctypes.c_longlong(len(recs)), outer, ctypes.c_ulonglong(seed),
+            ctypes.byref(res),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, MfmaSweepResult(fmt)
+        return rc, MfmaSweepResult._from_c(fmt, res)
+
+    def mx_sweep(self, dev: int, fmt: str = "fp4", workgroups: int = 0, outer: int = 0,
+                 seed: int = DEFAULT_MX_SWEEP_SEED) -> MfmaSweepResult:
+        """As ``mfma_sweep``, on the block-scaled 16x16x128 instruction in
+        ``fmt``: every SIMD of every CU issues fp4 / fp6 MFMAs, each wave
+        checked bit-exactly. 65536 FLOP per MFMA; the TFLOP/s caveat of
+        ``mfma_sweep`` applies."""
+        res = _MfmaSweepResultC()
+        tflops = ctypes.c_double(0)
+        rc = self.lib.na_mx_sweep(
+            dev, self._mx_format(fmt), workgroups, outer, ctypes.c_ulonglong(seed),
+            ctypes.byref(res), ctypes.byref(tflops),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            raise NodeAgentError(f"mx_sweep({dev}, {fmt}): {self._err()}")
+        return MfmaSweepResult._from_c(fmt, res, tflops.value)
+
+    def _run_mx_sweep(self, g: GPUReport) -> None:
+        for fmt in MX_SWEEP_FORMATS:
+            res = self.mx_sweep(g.index, fmt)
+            g.mx_sweep_bad_waves += res.bad_waves
+            setattr(g, f"mx_sweep_{fmt}_tflops", round(res.tflops, 1))
+            if fmt == "fp4" and res.tflops < MIN_MX_SWEEP_TFLOPS:
+                g.problems.append(
+                    f"MX sweep fp4 {g.mx_sweep_fp4_tflops} TFLOP/s below floor "
+                    f"{MIN_MX_SWEEP_TFLOPS}"
+                )
+            if not res.ok:
+                g.problems.append(f"MX sweep {fmt}: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         if self.lib.na_p2p_matrix(n, buf) != 0:
@@ -555,7 +711,8 @@ class NodeAgent:
     # -- full health check ---------------------------------------------------
 
     def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
-              memtest_bytes: int = 0, mfma_sweep: bool = False) -> NodeReport:
+              memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
+              mx_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -567,7 +724,15 @@ class NodeAgent:
         bf16 and fp8 on every GPU: a wrong wave is a problem that names the
         unit it ran on, as is a bf16 rate under ``MIN_MFMA_SWEEP_TFLOPS``.
         ``mfma_sweep_units_seen`` below the CU count is reported, not a
-        problem. False (default) makes no sweep call."""
+        problem. False (default) makes no sweep call.
+
+        ``mx_checks`` additionally runs the single-wave MX checks of
+        ``MX_CHECK_KINDS`` (fp4, fp6, bf6, bf8 and mixed operands, per-lane
+        scales, scale byte select) on every GPU; a failed kind is a problem
+        that carries the first wrong word. ``mx_sweep`` additionally runs the
+        chip-wide sweep on the block-scaled instruction in fp4 and fp6: a
+        wrong wave is a problem that names its unit, as is an fp4 rate under
+        ``MIN_MX_SWEEP_TFLOPS``. False (default) calls nothing new."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -603,6 +768,10 @@ class NodeAgent:
                     self._run_memtest(g, memtest_bytes)
                 if mfma_sweep:
                     self._run_mfma_sweep(g)
+                if mx_checks:
+                    self._run_mx_checks(g)
+                if mx_sweep:
+                    self._run_mx_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -707,6 +876,20 @@ def main(argv=None) -> int:
         "(integer operands: not comparable to GEMM benchmarks) and the in-kernel clock",
     )
     ap.add_argument(
+        "--mx-checks",
+        action="store_true",
+        help="also run the single-wave checks of the block-scaled MX matrix instructions: "
+        "fp4, fp6, bf6, bf8 and fp8 x fp4 operands, per-lane E8M0 scales, every scale byte "
+        "select, both tile shapes, and every code point of the sub-byte formats",
+    )
+    ap.add_argument(
+        "--mx-sweep",
+        action="store_true",
+        help="also run the chip-wide sweep on the block-scaled 16x16x128 instruction in fp4 "
+        "and fp6 on every GPU: as --mfma-sweep, each wave checked bit-exactly and a wrong one "
+        "attributed to its XCC/SE/SH/CU/SIMD; reports sustained TFLOP/s per format",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -720,6 +903,8 @@ def main(argv=None) -> int:
             bw_bytes=args.bw_bytes,
             memtest_bytes=args.memtest_bytes,
             mfma_sweep=args.mfma_sweep,
+            mx_checks=args.mx_checks,
+            mx_sweep=args.mx_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

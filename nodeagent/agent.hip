@@ -11,7 +11,9 @@
 // the ML workloads live on (one kernel template over the operand traits of
 // mfma_frag.h, run and verified by na_mfma_check_run / _verify), an opt-in
 // chip-wide matrix-core sweep (one wave per SIMD of every CU, mfmasweep.h),
-// and the xGMI peer-to-peer link matrix.
+// opt-in single-wave checks and the same sweep on the block-scaled MX
+// instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h), and the
+// xGMI peer-to-peer link matrix.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
 // consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -189,8 +192,61 @@ struct tile_operands {
     }
 };
 
+// MX kinds (the mfma_mxs_* traits; formulas normative, and carried as an
+// independent numpy copy by tests/test_nodeagent_mxchecks.py). Unlike
+// tile_a, both operands vary in k, so an error in how K is laid out across
+// lanes or packed inside a fragment changes D; blk = k / 32 is the scale
+// block, and every D is a multiple of 1/4 below 2^13, exact in any order.
+__device__ __host__ inline int mx_tile_a(int i, int k) {
+    return (i * 5 + k * 3 + (k >> 4)) % 7 - 3;
+}
+__device__ __host__ inline int mx_tile_b(int k, int j) {
+    return (k * 2 + j * 3 + (k >> 5)) % 5 - 2;
+}
+__device__ __host__ inline int mx_tile_ea(int i, int blk) { return (i + 2 * blk) % 4 - 1; }
+__device__ __host__ inline int mx_tile_eb(int blk, int j) { return (j * 3 + blk) % 3 - 1; }
+
+// mx_tile_operands: D = sum_blk 2^(ea+eb) sum_{k in blk} a(i,k) b(k,j), the
+// scales as E8M0 bytes 127 + e.
+struct mx_tile_operands : tile_operands {
+    template <typename T>
+    static __device__ void fill(mx_frag& a, mx_frag& b, int l) {
+        const int rc = l % T::MN, g = l / T::MN;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            T::set_a(a, i, mx_encode_int(T::FMT_A, mx_tile_a(rc, T::k_a(g, i))));
+            T::set_b(b, i, mx_encode_int(T::FMT_B, mx_tile_b(T::k_b(g, i), rc)));
+        }
+        T::scale_a(a, 127 + mx_tile_ea(rc, g));
+        T::scale_b(b, 127 + mx_tile_eb(g, rc));
+    }
+};
+
+// mx_code_operands (16x16x128, B in E2M1): A[i][k] is code (i*37 + k*11) % n
+// of A's format, n its number of codes; B[k][j] = 1.0 where k % 16 == j, else
+// 0; scales 1.0. D[i][j] = sum_{m<8} decode(code(i, j + 16m)) pushes every
+// code through A's decoder (11 is odd, so a row's 128 k cover all n codes).
+__device__ __host__ inline unsigned mx_code_a(int fmt, int i, int k) {
+    return (unsigned)(i * 37 + k * 11) % (1u << mx_bits(fmt));
+}
+
+struct mx_code_operands : tile_operands {
+    template <typename T>
+    static __device__ void fill(mx_frag& a, mx_frag& b, int l) {
+        const int rc = l % 16, g = l / 16;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            T::set_a(a, i, mx_code_a(T::FMT_A, rc, T::k_a(g, i)));
+            T::set_b(b, i, T::k_b(g, i) % 16 == rc ? mx_encode_int(MX_E2M1, 1) : 0u);
+        }
+        T::scale_a(a, 127);
+        T::scale_b(b, 127);
+    }
+};
+
 // out: T::MN * T::MN words. Launch with one wave (64 threads): MFMA is a
-// per-wave instruction. scale_a reaches the MX kind only.
+// per-wave instruction. scale_a reaches the fp8-only MX kind of mfma_frag.h;
+// the mfma_mxs_* traits carry their scales in the fragments.
 template <typename T, typename GEN>
 __global__ void mfma_check_kernel(void* __restrict__ out_, int scale_a) {
     typename T::word* __restrict__ out = static_cast<typename T::word*>(out_);
@@ -296,6 +352,17 @@ extern "C" int na_fma_selftest(int dev) {
     return NA_OK;
 }
 
+// One wave of a check kernel; its `words` raw 32-bit words go to out.
+static int check_launch(int dev, void (*kernel)(void*, int), int scale_a, void* out, int words) {
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<uint32_t> d;
+    HIP_CHECK(d.alloc((size_t)words));
+    kernel<<<dim3(1), dim3(64)>>>(d.p, scale_a);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, d.p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NA_OK;
+}
+
 // One row per kind of the single-wave MFMA checks (mfma_frag.h), in the
 // order of the kind codes. `label` opens the failure message. D of the MX
 // kinds is `mult` times the unscaled product.
@@ -344,13 +411,7 @@ static const mfma_check* mfma_check_args(const char* fn, int kind, const void* w
 extern "C" int na_mfma_check_run(int dev, int kind, void* out, int n_words) {
     const mfma_check* c = mfma_check_args("na_mfma_check_run", kind, out, n_words);
     if (c == nullptr) return NA_ERR_ARG;
-    HIP_CHECK(hipSetDevice(dev));
-    dev_buf<uint32_t> d;
-    HIP_CHECK(d.alloc((size_t)c->words()));
-    c->kernel<<<dim3(1), dim3(64)>>>(d.p, c->scale_a);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, d.p, (size_t)c->words() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return NA_OK;
+    return check_launch(dev, c->kernel, c->scale_a, out, c->words());
 }
 
 // Pure host code: compares the words of `kind` by value against the exact
@@ -406,6 +467,139 @@ extern "C" int na_mfma_bf16_tile32_check(int dev) {
 extern "C" int na_mfma_mx_tile_check(int dev) {
     int rc = mfma_check_one(dev, NA_MFMA_MX_TILE);
     return rc != NA_OK ? rc : mfma_check_one(dev, NA_MFMA_MX_TILE_X2);
+}
+
+// ---------------------------------------------------------------------------
+// Single-wave MX checks: every operand format, the per-lane scales and the
+// scale byte select of the f8f6f4 instructions (traits in mfma_frag.h)
+// ---------------------------------------------------------------------------
+
+// Pure host code, for tests of the encodings and the packing.
+extern "C" int na_mx_decode(int fmt, int code, float* value) {
+    if (fmt < 0 || fmt >= MX_FORMATS || code < 0 || code >= 1 << mx_bits(fmt) ||
+        value == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_mx_decode: need fmt in 0..%d (got %d), a code of its width (got %d) "
+                      "and a result pointer",
+                      MX_FORMATS - 1, fmt, code);
+        return NA_ERR_ARG;
+    }
+    *value = mx_decode(fmt, (unsigned)code);
+    return NA_OK;
+}
+
+// n codes (a multiple of 32: whole fragments) packed as a lane's fragment
+// registers are, fragment after fragment; words receives n * width / 32.
+extern "C" int na_mx_pack(int fmt, const int* codes, int n, uint32_t* words, int n_words) {
+    bool ok = fmt >= 0 && fmt < MX_FORMATS && codes != nullptr && words != nullptr && n > 0 &&
+              n % 32 == 0 && (long long)n_words * 32 >= (long long)n * mx_bits(fmt);
+    for (int i = 0; ok && i < n; ++i) ok = codes[i] >= 0 && codes[i] < 1 << mx_bits(fmt);
+    if (!ok) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_mx_pack: need fmt in 0..%d (got %d), n a positive multiple of 32 (got "
+                      "%d) of codes of that width, and room for n * width / 32 words (codes %p, "
+                      "words %p, n_words %d)",
+                      MX_FORMATS - 1, fmt, n, (const void*)codes, (void*)words, n_words);
+        return NA_ERR_ARG;
+    }
+    const int regs = mx_bits(fmt);  // 32 elements of `width` bits fill `width` registers
+    std::memset(words, 0, (size_t)(n / 32) * regs * sizeof(uint32_t));
+    for (int i = 0; i < n; ++i) {
+        uint32_t* frag = words + (i / 32) * regs;
+        mx_put(frag, fmt, i % 32, (unsigned)codes[i]);
+    }
+    return NA_OK;
+}
+
+// One row per kind, in the order of the NA_MX_* codes.
+struct mx_check {
+    const char* label;
+    void (*kernel)(void*, int);
+    int mn, k;
+    int code_fmt;  // format whose codes the kind enumerates, -1 for the tile kinds
+    int words() const { return mn * mn; }
+};
+
+template <typename T>
+static mx_check mx_tile_row(const char* label) {
+    return {label, mfma_check_kernel<T, mx_tile_operands>, T::MN, T::K, -1};
+}
+template <int FMT, int OA, int OB>
+static mx_check mx_code_row(const char* label) {
+    typedef mfma_mxs_16x16x128<FMT, MX_E2M1, OA, OB> T;
+    return {label, mfma_check_kernel<T, mx_code_operands>, T::MN, T::K, FMT};
+}
+
+// Between them the kinds select every byte of the scale register on each side.
+static const mx_check mx_checks[NA_MX_KINDS] = {
+    mx_tile_row<mfma_mxs_16x16x128<MX_E2M1, MX_E2M1, 1, 2>>("mx fp4 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E2M3, MX_E2M3, 2, 3>>("mx fp6 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E3M2, MX_E3M2, 3, 0>>("mx bf6 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E5M2, MX_E5M2, 0, 1>>("mx bf8 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E4M3, MX_E2M1, 2, 1>>("mx fp8 x fp4 tile"),
+    mx_tile_row<mfma_mxs_32x32x64<MX_E2M1, MX_E2M1, 3, 2>>("mx fp4 32x32 tile"),
+    mx_code_row<MX_E2M1, 1, 3>("mx fp4 codes"),
+    mx_code_row<MX_E2M3, 3, 1>("mx fp6 codes"),
+    mx_code_row<MX_E3M2, 2, 2>("mx bf6 codes"),
+};
+
+static float mx_check_want(const mx_check& c, int i, int j) {
+    float want = 0.f;  // every partial sum is exact
+    if (c.code_fmt >= 0) {
+        for (int m = 0; m < c.k / 16; ++m)
+            want += mx_decode(c.code_fmt, mx_code_a(c.code_fmt, i, j + 16 * m));
+        return want;
+    }
+    for (int blk = 0; blk < c.k / 32; ++blk) {
+        int dot = 0;
+        for (int k = blk * 32; k < blk * 32 + 32; ++k) dot += mx_tile_a(i, k) * mx_tile_b(k, j);
+        want += std::ldexp((float)dot, mx_tile_ea(i, blk) + mx_tile_eb(blk, j));
+    }
+    return want;
+}
+
+static const mx_check* mx_check_args(const char* fn, int kind, const void* words, int n_words) {
+    if (kind >= 0 && kind < NA_MX_KINDS && words != nullptr && n_words >= mx_checks[kind].words())
+        return &mx_checks[kind];
+    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                  "%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the "
+                  "32x32 tile (words %p, n_words %d)",
+                  fn, NA_MX_KINDS - 1, kind, words, n_words);
+    return nullptr;
+}
+
+// As na_mfma_check_run / na_mfma_check_verify, on the NA_MX_* kinds: every
+// word is a float32.
+extern "C" int na_mx_check_run(int dev, int kind, void* out, int n_words) {
+    const mx_check* c = mx_check_args("na_mx_check_run", kind, out, n_words);
+    if (c == nullptr) return NA_ERR_ARG;
+    return check_launch(dev, c->kernel, 0, out, c->words());
+}
+
+extern "C" int na_mx_check_verify(int kind, const void* words, int n_words) {
+    const mx_check* c = mx_check_args("na_mx_check_verify", kind, words, n_words);
+    if (c == nullptr) return NA_ERR_ARG;
+    const float* f = static_cast<const float*>(words);
+    for (int e = 0; e < c->words(); ++e) {
+        const int i = e / c->mn, j = e % c->mn;
+        const float want = mx_check_want(*c, i, j);
+        if (f[e] == want) continue;
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "%s: D[%d][%d] got %g want %g", c->label, i, j, f[e], want);
+        return NA_ERR_VERIFY;
+    }
+    return NA_OK;
+}
+
+// Every kind in turn, stopping at the first that fails.
+extern "C" int na_mx_checks(int dev) {
+    uint32_t words[1024];
+    for (int kind = 0; kind < NA_MX_KINDS; ++kind) {
+        int rc = na_mx_check_run(dev, kind, words, 1024);
+        if (rc == NA_OK) rc = na_mx_check_verify(kind, words, 1024);
+        if (rc != NA_OK) return rc;
+    }
+    return NA_OK;
 }
 
 extern "C" int na_lds_selftest(int dev, long long* bytes_tested) {
@@ -778,15 +972,15 @@ static uint64_t ms_geometric_sum(uint64_t q, uint64_t n) {
 }
 
 // sum over the wave's 64 lanes of P = d0 G^3 + d1 G^2 + d2 G + d3, where
-// d_i = D[(l>>4)*4+i][l&15] and D = (sum_t A_t)(sum_t B_t).
-static uint64_t ms_wave_p_sum(uint64_t base, uint64_t wave) {
-    int sa[16][32], sb[16][32];
+// d_i = D[(l>>4)*4+i][l&15] and D = (sum_t A_t)(sum_t B_t) over k_len.
+static uint64_t ms_wave_p_sum(uint64_t base, uint64_t wave, int k_len) {
+    int sa[16][MS_MAX_K], sb[16][MS_MAX_K];
     for (int r = 0; r < 16; ++r) {
-        for (int k = 0; k < 32; ++k) {
+        for (int k = 0; k < k_len; ++k) {
             sa[r][k] = sb[r][k] = 0;
             for (int t = 0; t < MS_FRAGS; ++t) {
-                sa[r][k] += ms_value(base, wave, 0, t, r, k);
-                sb[r][k] += ms_value(base, wave, 1, t, r, k);
+                sa[r][k] += ms_value(base, wave, 0, t, r, k, k_len);
+                sb[r][k] += ms_value(base, wave, 1, t, r, k, k_len);
             }
         }
     }
@@ -795,7 +989,7 @@ static uint64_t ms_wave_p_sum(uint64_t base, uint64_t wave) {
         uint64_t p = 0;
         for (int i = 0; i < 4; ++i) {
             int row = (l >> 4) * 4 + i, col = l & 15, d = 0;
-            for (int k = 0; k < 32; ++k) d += sa[row][k] * sb[col][k];
+            for (int k = 0; k < k_len; ++k) d += sa[row][k] * sb[col][k];
             p = p * MS_G + (uint64_t)(int64_t)d;
         }
         sum += p;
@@ -803,36 +997,51 @@ static uint64_t ms_wave_p_sum(uint64_t base, uint64_t wave) {
     return sum;
 }
 
+// The sweep comes in two families that share everything below: the
+// na_mfma_sweep* entry points on the non-scaled K = 32 instructions and the
+// na_mx_sweep* ones on the block-scaled K = 128 instruction. A family's
+// public code c (dtype or format, 0 or 1) is kernel variant `first` + c.
+struct ms_family {
+    const char* prefix;  // opens the argument errors
+    const char* label;   // opens the verdict
+    const char* codes;   // the two public codes, for the argument error
+    int first, k_len;
+};
+static const ms_family ms_mfma = {"na_mfma_sweep", "mfma sweep", "dtype 0 (bf16) or 1 (fp8)",
+                                  MS_BF16, 32};
+static const ms_family ms_mx = {"na_mx_sweep", "mx sweep", "format 0 (fp4) or 1 (fp6)", MS_FP4,
+                                MS_MAX_K};
+
 // Pure host code. All folds produce the same D, so the per-lane recurrence
 // c = c G + d_i collapses to c = P S(outer), S(n) = sum_{j<n} G^{4j}, and the
 // wave checksum to S(outer) * sum_l P_l.
-extern "C" int na_mfma_sweep_expected(unsigned long long seed, unsigned long long wave, int outer,
-                                      uint64_t* checksum) {
+static int ms_expected(const ms_family& fam, unsigned long long seed, unsigned long long wave,
+                       int outer, uint64_t* checksum) {
     if (outer < 1 || checksum == nullptr) {
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_mfma_sweep_expected: need outer >= 1 (got %d) and a result pointer",
+                      "%s_expected: need outer >= 1 (got %d) and a result pointer", fam.prefix,
                       outer);
         return NA_ERR_ARG;
     }
     const uint64_t g2 = MS_G * MS_G;
-    *checksum = ms_geometric_sum(g2 * g2, (uint64_t)outer) * ms_wave_p_sum(seed * MS_G, wave);
+    *checksum = ms_geometric_sum(g2 * g2, (uint64_t)outer) *
+                ms_wave_p_sum(seed * MS_G, wave, fam.k_len);
     return NA_OK;
 }
 
 // One launch of `workgroups` x 4 waves, HIP-event timed; out receives the
 // 4 * workgroups records. Argument errors are detected before any HIP call.
-extern "C" int na_mfma_sweep_run(int dev, int dtype, int workgroups, int outer,
-                                 unsigned long long seed, na_mfma_record* out, long long n_out,
-                                 double* ms) {
-    if ((dtype != MS_BF16 && dtype != MS_FP8) || workgroups < 1 ||
-        workgroups > NA_MFMA_MAX_WORKGROUPS || outer < 1 || outer > NA_MFMA_MAX_OUTER ||
-        out == nullptr || n_out < (long long)workgroups * MS_WAVES_PER_WG) {
+static int ms_run(const ms_family& fam, int dev, int code, int workgroups, int outer,
+                  unsigned long long seed, na_mfma_record* out, long long n_out, double* ms) {
+    if ((code != 0 && code != 1) || workgroups < 1 || workgroups > NA_MFMA_MAX_WORKGROUPS ||
+        outer < 1 || outer > NA_MFMA_MAX_OUTER || out == nullptr ||
+        n_out < (long long)workgroups * MS_WAVES_PER_WG) {
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_mfma_sweep_run: need dtype 0 (bf16) or 1 (fp8) (got %d), workgroups in "
+                      "%s_run: need %s (got %d), workgroups in "
                       "1..%d (got %d), outer in 1..%d (got %d) and room for 4 records per "
                       "workgroup (out %p, n_out %lld)",
-                      dtype, NA_MFMA_MAX_WORKGROUPS, workgroups, NA_MFMA_MAX_OUTER, outer,
-                      (void*)out, n_out);
+                      fam.prefix, fam.codes, code, NA_MFMA_MAX_WORKGROUPS, workgroups,
+                      NA_MFMA_MAX_OUTER, outer, (void*)out, n_out);
         return NA_ERR_ARG;
     }
     HIP_CHECK(hipSetDevice(dev));
@@ -852,10 +1061,10 @@ extern "C" int na_mfma_sweep_run(int dev, int dtype, int workgroups, int outer,
     const mt_u64 base = seed * MS_G;
     dim3 grid((unsigned)workgroups), block(MS_BLOCK);
     HIP_CHECK(hipEventRecord(ev.e[0]));
-    if (dtype == MS_BF16)
-        mfma_sweep_kernel<MS_BF16><<<grid, block, lds_bytes>>>(d.p, base, outer);
-    else
-        mfma_sweep_kernel<MS_FP8><<<grid, block, lds_bytes>>>(d.p, base, outer);
+    static void (*const kernels[MS_DTYPES])(na_mfma_record*, mt_u64, int) = {
+        mfma_sweep_kernel<MS_BF16>, mfma_sweep_kernel<MS_FP8>, mfma_sweep_kernel<MS_FP4>,
+        mfma_sweep_kernel<MS_FP6>};
+    kernels[fam.first + code]<<<grid, block, lds_bytes>>>(d.p, base, outer);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ev.e[1]));
     HIP_CHECK(hipEventSynchronize(ev.e[1]));
@@ -873,13 +1082,13 @@ static inline uint32_t ms_cu_key(const na_mfma_record& r) {
 // Pure host code: record i is wave i. A wave is bad when its checksum is
 // not the expected one or it does not carry its own index. Returns
 // NA_ERR_VERIFY on any bad wave; *res is filled either way.
-extern "C" int na_mfma_sweep_verify(const na_mfma_record* recs, long long n, int outer,
-                                    unsigned long long seed, na_mfma_sweep_result* res) {
+static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long n, int outer,
+                     unsigned long long seed, na_mfma_sweep_result* res) {
     if (recs == nullptr || n < 1 || outer < 1 || res == nullptr) {
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_mfma_sweep_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) "
+                      "%s_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) "
                       "and a result pointer",
-                      n, outer);
+                      fam.prefix, n, outer);
         return NA_ERR_ARG;
     }
     std::memset(res, 0, sizeof(*res));
@@ -898,7 +1107,8 @@ extern "C" int na_mfma_sweep_verify(const na_mfma_record* recs, long long n, int
             res->units_seen++;
         }
         if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
-        if (r.checksum == s * ms_wave_p_sum(base, (uint64_t)i) && r.wave == (uint64_t)i) continue;
+        if (r.checksum == s * ms_wave_p_sum(base, (uint64_t)i, fam.k_len) && r.wave == (uint64_t)i)
+            continue;
         res->bad_waves++;
         if (!bad[key]) {
             bad[key] = true;
@@ -922,9 +1132,9 @@ extern "C" int na_mfma_sweep_verify(const na_mfma_record* recs, long long n, int
     if (res->bad_waves == 0) return NA_OK;
     const uint32_t* u = res->first_bad_unit;
     std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "mfma sweep: %llu of %llu waves wrong on %llu CU(s), first wave %llu on "
+                  "%s: %llu of %llu waves wrong on %llu CU(s), first wave %llu on "
                   "xcc%u.se%u.sh%u.cu%u.simd%u",
-                  (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                  fam.label, (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
                   (unsigned long long)res->bad_units, (unsigned long long)res->first_bad_wave,
                   u[0], u[1], u[2], u[3], u[4]);
     return NA_ERR_VERIFY;
@@ -932,14 +1142,15 @@ extern "C" int na_mfma_sweep_verify(const na_mfma_record* recs, long long n, int
 
 // Whole sweep: one untimed warm-up launch, the timed launch, the verify.
 // workgroups 0 = 4 per CU, outer 0 = NA_MFMA_DEFAULT_OUTER. *tflops counts
-// 64 MFMAs of 16384 FLOP per wave and fold over the event time.
-extern "C" int na_mfma_sweep(int dev, int dtype, int workgroups, int outer,
-                             unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
+// 64 MFMAs of 512 K FLOP (16384, or 65536 for the MX family) per wave and
+// fold over the event time.
+static int ms_sweep(const ms_family& fam, int dev, int code, int workgroups, int outer,
+                    unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
     if (res == nullptr || workgroups < 0 || workgroups > NA_MFMA_MAX_WORKGROUPS || outer < 0) {
         std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_mfma_sweep: need workgroups in 0..%d (got %d), outer >= 0 (got %d) and "
+                      "%s: need workgroups in 0..%d (got %d), outer >= 0 (got %d) and "
                       "a result pointer",
-                      NA_MFMA_MAX_WORKGROUPS, workgroups, outer);
+                      fam.prefix, NA_MFMA_MAX_WORKGROUPS, workgroups, outer);
         return NA_ERR_ARG;
     }
     if (outer == 0) outer = NA_MFMA_DEFAULT_OUTER;
@@ -951,11 +1162,51 @@ extern "C" int na_mfma_sweep(int dev, int dtype, int workgroups, int outer,
     std::vector<na_mfma_record> recs((size_t)workgroups * MS_WAVES_PER_WG);
     double ms = 0.0;
     for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
-        int rc = na_mfma_sweep_run(dev, dtype, workgroups, outer, seed, recs.data(),
-                                   (long long)recs.size(), &ms);
+        int rc = ms_run(fam, dev, code, workgroups, outer, seed, recs.data(),
+                        (long long)recs.size(), &ms);
         if (rc != NA_OK) return rc;
     }
     if (tflops)
-        *tflops = (double)recs.size() * outer * MS_MFMA_PER_FOLD * MS_FLOP_PER_MFMA / (ms * 1e9);
-    return na_mfma_sweep_verify(recs.data(), (long long)recs.size(), outer, seed, res);
+        *tflops = (double)recs.size() * outer * MS_MFMA_PER_FOLD * MS_FLOP_PER_MFMA_K * fam.k_len /
+                  (ms * 1e9);
+    return ms_verify(fam, recs.data(), (long long)recs.size(), outer, seed, res);
+}
+
+extern "C" int na_mfma_sweep_expected(unsigned long long seed, unsigned long long wave, int outer,
+                                      uint64_t* checksum) {
+    return ms_expected(ms_mfma, seed, wave, outer, checksum);
+}
+extern "C" int na_mfma_sweep_run(int dev, int dtype, int workgroups, int outer,
+                                 unsigned long long seed, na_mfma_record* out, long long n_out,
+                                 double* ms) {
+    return ms_run(ms_mfma, dev, dtype, workgroups, outer, seed, out, n_out, ms);
+}
+extern "C" int na_mfma_sweep_verify(const na_mfma_record* recs, long long n, int outer,
+                                    unsigned long long seed, na_mfma_sweep_result* res) {
+    return ms_verify(ms_mfma, recs, n, outer, seed, res);
+}
+extern "C" int na_mfma_sweep(int dev, int dtype, int workgroups, int outer,
+                             unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
+    return ms_sweep(ms_mfma, dev, dtype, workgroups, outer, seed, res, tflops);
+}
+
+// The same four on v_mfma_scale_f32_16x16x128_f8f6f4 at scales of 1.0:
+// format 0 = fp4 (E2M1), 1 = fp6 (E2M3), and 65536 FLOP per MFMA. Both
+// formats give the same checksums.
+extern "C" int na_mx_sweep_expected(unsigned long long seed, unsigned long long wave, int outer,
+                                    uint64_t* checksum) {
+    return ms_expected(ms_mx, seed, wave, outer, checksum);
+}
+extern "C" int na_mx_sweep_run(int dev, int format, int workgroups, int outer,
+                               unsigned long long seed, na_mfma_record* out, long long n_out,
+                               double* ms) {
+    return ms_run(ms_mx, dev, format, workgroups, outer, seed, out, n_out, ms);
+}
+extern "C" int na_mx_sweep_verify(const na_mfma_record* recs, long long n, int outer,
+                                  unsigned long long seed, na_mfma_sweep_result* res) {
+    return ms_verify(ms_mx, recs, n, outer, seed, res);
+}
+extern "C" int na_mx_sweep(int dev, int format, int workgroups, int outer,
+                           unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
+    return ms_sweep(ms_mx, dev, format, workgroups, outer, seed, res, tflops);
 }

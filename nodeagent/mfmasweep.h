@@ -1,6 +1,6 @@
 // Chip-wide matrix-core sweep for the MI355X node agent (included from
 // agent.hip; operand packing and MFMA calls are mfma_frag.h's bf16 and fp8
-// 16x16x32 traits).
+// 16x16x32 traits and, for the MX sweep, its unit-scale 16x16x128 trait).
 //
 // The single-wave MFMA checks in agent.hip run on one SIMD of one CU. This
 // kernel puts one wave on every SIMD of every CU, has each run a long MFMA
@@ -28,6 +28,11 @@
 // D = (sum_t A_t)(sum_t B_t). After each fold, per lane and for i = 0..3:
 //   c = c*G + (uint64)(int64)D[(l>>4)*4+i][l&15]
 // The wave checksum is sum_l c_l.
+//
+// The MX sweep (fp4 = E2M1, fp6 = E2M3 on v_mfma_scale_f32_16x16x128_f8f6f4,
+// every scale 1.0) is the same kernel on K = 128: k runs over 0..127 with
+// idx = (...)*128 + k and lane l holds k = (l>>4)*32+i, so |D| <= 49152,
+// still exact, and fp4 and fp6 give the same checksums.
 
 #pragma once
 
@@ -35,6 +40,7 @@
 
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 
 #include "memtest.h"
 #include "mfma_frag.h"
@@ -43,10 +49,13 @@
 #define MS_WAVES_PER_WG (MS_BLOCK / 64)
 #define MS_FRAGS 8
 #define MS_MFMA_PER_FOLD (MS_FRAGS * MS_FRAGS)
-#define MS_FLOP_PER_MFMA 16384.0  // 16 x 16 x 32 x 2
+#define MS_FLOP_PER_MFMA_K 512.0  // 16 x 16 x 2, per unit of K
+#define MS_MAX_K 128
 #define MS_G 0x9E3779B97F4A7C15ULL
 
-enum { MS_BF16 = 0, MS_FP8 = 1 };
+// MS_BF16 and MS_FP8 are the dtype codes of na_mfma_sweep*; the MX sweep's
+// format f (0 = fp4, 1 = fp6) is MS_FP4 + f.
+enum { MS_BF16 = 0, MS_FP8 = 1, MS_FP4 = 2, MS_FP6 = 3, MS_DTYPES };
 
 // s_getreg operand: SIZE-1 in 15:11, OFFSET in 10:6, register id in 5:0
 // (encodings: amd_device_functions.h). HW_ID is register 4, XCC_ID 20.
@@ -59,8 +68,11 @@ typedef struct {
     uint32_t wave, xcc, se, sh, cu, simd;
 } na_mfma_record;
 
-__device__ __host__ inline int ms_value(mt_u64 base, mt_u64 w, int m, int t, int r, int k) {
-    mt_u64 idx = ((((w * 2 + (mt_u64)m) * 8 + (mt_u64)t) * 16 + (mt_u64)r) * 32 + (mt_u64)k);
+// k_len: K of the MFMA, 32 or 128.
+__device__ __host__ inline int ms_value(mt_u64 base, mt_u64 w, int m, int t, int r, int k,
+                                        int k_len) {
+    mt_u64 idx =
+        ((((w * 2 + (mt_u64)m) * 8 + (mt_u64)t) * 16 + (mt_u64)r) * (mt_u64)k_len + (mt_u64)k);
     unsigned e = (unsigned)(mt_mix64(base + idx) >> 40);  // 24 bits
     return m == 0 ? (int)(e % 7u) - 3 : (int)(e % 5u) - 2;
 }
@@ -68,8 +80,11 @@ __device__ __host__ inline int ms_value(mt_u64 base, mt_u64 w, int m, int t, int
 #if defined(__gfx950__)
 
 template <int DTYPE>
-using ms_traits = typename std::conditional<DTYPE == MS_BF16, mfma_bf16_16x16x32,
-                                            mfma_fp8_16x16x32>::type;
+using ms_traits = typename std::conditional<
+    DTYPE == MS_BF16, mfma_bf16_16x16x32,
+    typename std::conditional<
+        DTYPE == MS_FP8, mfma_fp8_16x16x32,
+        mfma_mx1_16x16x128<DTYPE == MS_FP4 ? MX_E2M1 : MX_E2M3>>::type>::type;
 
 // One fold. The operands never change, so without the empty asm the
 // compiler may compute D once and drop the loop; "+v" tells it each A
@@ -87,6 +102,26 @@ __device__ inline f32x4 ms_fold(typename T::frag (&a)[MS_FRAGS],
         for (int tb = 0; tb < MS_FRAGS; ++tb) acc = T::mfma(a[ta], b[tb], acc);
     }
     return acc;
+}
+
+// Fragment t of matrix m as lane l holds it: T::PER_LANE consecutive k of
+// row (A) or column (B) l&15.
+template <typename T>
+__device__ inline typename T::frag ms_fragment(mt_u64 base, mt_u64 w, int m, int t, int l) {
+    typename T::frag f{};
+    const int r = l & 15, k0 = (l >> 4) * T::PER_LANE;
+#pragma unroll
+    for (int i = 0; i < T::PER_LANE; ++i) T::set(f, i, ms_value(base, w, m, t, r, k0 + i, T::K));
+    return f;
+}
+
+// All fragments, unrolled by pack expansion: with 32 hashed elements per MX
+// fragment a loop over t is past the size to which a pragma unrolls, and a
+// fragment array indexed at run time would live in scratch.
+template <typename T, int... Ts>
+__device__ inline void ms_fill(typename T::frag (&a)[MS_FRAGS], typename T::frag (&b)[MS_FRAGS],
+                               mt_u64 base, mt_u64 w, int l, std::integer_sequence<int, Ts...>) {
+    ((a[Ts] = ms_fragment<T>(base, w, 0, Ts, l), b[Ts] = ms_fragment<T>(base, w, 1, Ts, l)), ...);
 }
 
 __device__ inline mt_u64 ms_update(mt_u64 c, f32x4 d) {
@@ -116,17 +151,7 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
     const mt_u64 w = (mt_u64)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6);
 
     frag a[MS_FRAGS], b[MS_FRAGS];
-    const int r = l & 15, k0 = (l >> 4) * 8;
-#pragma unroll
-    for (int t = 0; t < MS_FRAGS; ++t) {
-        a[t] = frag{};
-        b[t] = frag{};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            T::set(a[t], i, ms_value(base, w, 0, t, r, k0 + i));
-            T::set(b[t], i, ms_value(base, w, 1, t, r, k0 + i));
-        }
-    }
+    ms_fill<T>(a, b, base, w, l, std::make_integer_sequence<int, MS_FRAGS>{});
 
     // The stamps bracket the whole loop, go only into the record, and no
     // output is computed from them.
