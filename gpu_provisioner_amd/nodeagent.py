@@ -6,7 +6,7 @@ evidence. Fails LOUDLY if the native library is missing on a GPU machine —
 there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
-[--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep]``
+[--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -92,6 +92,22 @@ MX_SWEEP_FORMATS = {"fp4": 0, "fp6": 1}
 # floor above and with its caveat: not comparable to GEMM benchmarks.
 # 0 disables the floor.
 MIN_MX_SWEEP_TFLOPS = 5370.5
+
+# Chip-wide LDS sweep (nodeagent/ldssweep.h). The default seed is "MI355XLS";
+# a record carries one checksum per phase, in this order.
+DEFAULT_LDS_SWEEP_SEED = 0x4D493335_35584C53
+LDS_SWEEP_PHASES = ("b32", "b128", "dma16", "dma4", "dma12", "tr16", "atomic", "stream")
+LDS_SWEEP_GRANULE = 4096  # lds_bytes is a multiple of this
+LDS_SWEEP_MAX_BYTES = 160 * 1024
+LDS_SWEEP_MAX_LISTED = 8
+LDS_SWEEP_PEAK_BYTES_PER_CLK = 256  # what a CU's LDS delivers per clock: a ceiling, no floor
+NO_BAD_WORKGROUP = (1 << 64) - 1
+# Floor of the default sweep's chip-wide stream rate: 0.70 x the 117806.3 GB/s
+# median of five processes on MI355X (profiles/lds_sweep_mi355x.txt; 195 of
+# the LDS's 256 bytes per clock and CU). The device-to-device spread of LDS
+# loops has not been measured; 0.70 is borrowed from the MFMA floor above.
+# 0 disables the floor.
+MIN_LDS_SWEEP_GBS = 82464.4
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -231,6 +247,109 @@ class MfmaSweepResult:
         )
 
 
+class LdsRecord(ctypes.Structure):
+    """One workgroup of the LDS sweep (``na_lds_record``): a checksum per
+    phase of ``LDS_SWEEP_PHASES``, the in-kernel diagnosis (count of bad
+    words, LDS byte offset of the first, OR of got^want, and the phase they
+    were seen in), the s_memtime / s_memrealtime deltas around the stream
+    phase, its index and the CU it ran on."""
+
+    _fields_ = [
+        ("checksum", ctypes.c_uint64 * len(LDS_SWEEP_PHASES)),
+        ("bad_words", ctypes.c_uint64),
+        ("first_bad_offset", ctypes.c_uint64),
+        ("xor_mask", ctypes.c_uint64),
+        ("cycles", ctypes.c_uint64),
+        ("realtime", ctypes.c_uint64),
+        ("workgroup", ctypes.c_uint32),
+        ("bad_phase", ctypes.c_uint32),
+        ("xcc", ctypes.c_uint32),
+        ("se", ctypes.c_uint32),
+        ("sh", ctypes.c_uint32),
+        ("cu", ctypes.c_uint32),
+    ]
+
+
+class _LdsSweepResultC(ctypes.Structure):
+    _fields_ = [
+        ("workgroups", ctypes.c_uint64),
+        ("bad_workgroups", ctypes.c_uint64),
+        ("units_seen", ctypes.c_uint64),
+        ("bad_units", ctypes.c_uint64),
+        ("first_bad_workgroup", ctypes.c_uint64),
+        ("bad_words", ctypes.c_uint64),
+        ("first_bad_offset", ctypes.c_uint64),
+        ("xor_mask", ctypes.c_uint64),
+        ("clock_mhz", ctypes.c_double),
+        ("median_bytes_per_clk", ctypes.c_double),
+        ("min_bytes_per_clk", ctypes.c_double),
+        ("max_bytes_per_clk", ctypes.c_double),
+        ("first_bad_unit", ctypes.c_uint32 * 4),
+        ("first_bad_phase", ctypes.c_uint32),
+        ("listed", ctypes.c_uint32),
+        ("bad_list", (ctypes.c_uint32 * 4) * LDS_SWEEP_MAX_LISTED),
+    ]
+
+
+@dataclass
+class LdsSweepResult:
+    """Outcome of an LDS sweep verify. A *unit* is a CU, ``(xcc, se, sh,
+    cu)``; ``bad_cus`` lists the first distinct failing ones (at most
+    ``LDS_SWEEP_MAX_LISTED``), the first being that of
+    ``first_bad_workgroup``. ``first_bad_phase`` names the first failing phase
+    of that workgroup ("index" when its record only sits in the wrong place);
+    ``bad_words`` / ``first_bad_offset`` / ``xor_mask`` are the kernel's own
+    diagnosis when that phase compares words (b32, b128, dma*). The rates are
+    the stream phase's bytes per shader clock and CU over the workgroups;
+    ``gbs`` is 0 when only a verify was done."""
+
+    workgroups: int = 0
+    bad_workgroups: int = 0
+    units_seen: int = 0
+    bad_units: int = 0
+    first_bad_workgroup: int = NO_BAD_WORKGROUP
+    first_bad_phase: str = ""
+    bad_words: int = 0
+    first_bad_offset: int = NO_BAD_OFFSET
+    xor_mask: int = 0
+    bad_cus: list = field(default_factory=list)
+    clock_mhz: float = 0.0
+    median_bytes_per_clk: float = 0.0
+    min_bytes_per_clk: float = 0.0
+    max_bytes_per_clk: float = 0.0
+    gbs: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.bad_workgroups == 0
+
+    def describe(self) -> str:
+        names = ", ".join(mfma_unit_name(u) for u in self.bad_cus)
+        more = ", ..." if len(self.bad_cus) == LDS_SWEEP_MAX_LISTED else ""
+        where = ""
+        if self.first_bad_offset != NO_BAD_OFFSET:
+            where = (
+                f", {self.bad_words} bad words, first at LDS offset {self.first_bad_offset:#x} "
+                f"(bank {self.first_bad_offset // 4 % 64}), failing bits {self.xor_mask:#010x}"
+            )
+        return (
+            f"{self.bad_workgroups} of {self.workgroups} workgroups wrong on {self.bad_units} "
+            f"CU(s): {names}{more}; first in phase {self.first_bad_phase}{where}"
+        )
+
+    @classmethod
+    def _from_c(cls, res: "_LdsSweepResultC", gbs: float = 0.0):
+        phase = ""
+        if res.first_bad_workgroup != NO_BAD_WORKGROUP:
+            phase = (LDS_SWEEP_PHASES + ("index",))[min(res.first_bad_phase, len(LDS_SWEEP_PHASES))]
+        return cls(
+            res.workgroups, res.bad_workgroups, res.units_seen, res.bad_units,
+            res.first_bad_workgroup, phase, res.bad_words, res.first_bad_offset, res.xor_mask,
+            [tuple(res.bad_list[i]) for i in range(res.listed)], res.clock_mhz,
+            res.median_bytes_per_clk, res.min_bytes_per_clk, res.max_bytes_per_clk, gbs,
+        )
+
+
 def _load_lib() -> ctypes.CDLL:
     for p in _SEARCH_PATHS:
         if os.path.exists(p):
@@ -255,6 +374,11 @@ class GPUReport:
     mfma_fp8_ok: bool = False
     lds_ok: bool = False
     lds_bytes_tested: int = 0
+    # chip-wide LDS sweep (opt-in; all "not run" by default)
+    lds_sweep_gbs: float = 0.0
+    lds_sweep_min_cu_bytes_per_clk: float = 0.0
+    lds_sweep_units_seen: int = 0
+    lds_sweep_bad_workgroups: int = 0
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -693,6 +817,97 @@ class NodeAgent:
             if not res.ok:
                 g.problems.append(f"MX sweep {fmt}: {res.describe()}")
 
+    # -- chip-wide LDS sweep ----------------------------------------------------
+
+    def lds_sweep_allocation(self, dev: int) -> int:
+        """Bytes of LDS a workgroup of the sweep holds, and tests when
+        ``lds_bytes`` is 0: the device's per-workgroup maximum, at most
+        160 KiB."""
+        out = ctypes.c_longlong(0)
+        if self.lib.na_lds_sweep_allocation(dev, ctypes.byref(out)) != NA_OK:
+            raise NodeAgentError(f"lds_sweep_allocation({dev}): {self._err()}")
+        return out.value
+
+    def lds_sweep_expected(self, workgroup: int, lds_bytes: int, iters: int,
+                           seed: int = DEFAULT_LDS_SWEEP_SEED) -> list:
+        """The checksums workgroup ``workgroup`` must report, one per phase of
+        ``LDS_SWEEP_PHASES``, testing ``lds_bytes`` (explicit here: a multiple
+        of 4096 up to 160 KiB) with ``iters`` stream passes (host arithmetic
+        only; needs no GPU)."""
+        out = (ctypes.c_uint64 * len(LDS_SWEEP_PHASES))()
+        rc = self.lib.na_lds_sweep_expected(
+            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(workgroup), ctypes.c_longlong(lds_bytes),
+            iters, out, len(out),
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"lds_sweep_expected: {self._err()}")
+        return list(out)
+
+    def lds_sweep_run(self, dev: int, workgroups: int = 1, lds_bytes: int = 0, iters: int = 1,
+                      seed: int = DEFAULT_LDS_SWEEP_SEED) -> tuple:
+        """One launch of ``workgroups`` workgroups, each through every phase
+        on the leading ``lds_bytes`` of its LDS (0 = all of it) with ``iters``
+        stream passes. Returns ``(records, ms)``: a ctypes array of
+        ``LdsRecord`` (record i is workgroup i) and the HIP-event time."""
+        n = max(workgroups, 0)
+        recs = (LdsRecord * max(n, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_lds_sweep_run(
+            dev, workgroups, ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed),
+            recs, ctypes.c_longlong(n), ctypes.byref(ms),
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"lds_sweep_run({dev}): {self._err()}")
+        return recs, ms.value
+
+    def lds_sweep_verify(self, recs, lds_bytes: int, iters: int,
+                         seed: int = DEFAULT_LDS_SWEEP_SEED) -> tuple:
+        """Compare every record against the host reference (``lds_bytes``
+        explicit, as for ``lds_sweep_expected``). Returns ``(rc,
+        LdsSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad workgroup, and
+        ``na_last_error`` then names the first failing phase and CU."""
+        res = _LdsSweepResultC()
+        rc = self.lib.na_lds_sweep_verify(
+            recs, ctypes.c_longlong(len(recs)), ctypes.c_longlong(lds_bytes), iters,
+            ctypes.c_ulonglong(seed), ctypes.byref(res),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, LdsSweepResult()
+        return rc, LdsSweepResult._from_c(res)
+
+    def lds_sweep(self, dev: int, workgroups: int = 0, lds_bytes: int = 0, iters: int = 0,
+                  seed: int = DEFAULT_LDS_SWEEP_SEED) -> LdsSweepResult:
+        """Run one workgroup at a time on every CU through every LDS access
+        path — 32- and 128-bit accesses, LDS-DMA at 16, 4 and 12 bytes, the
+        transposed read, atomics — and a timed read stream (``workgroups`` 0
+        = 4 per CU, ``lds_bytes`` 0 = the whole allocation, ``iters`` 0 = the
+        default pass count), verify every phase of every workgroup bit-exactly
+        against the host reference, and report the stream rate per CU and
+        chip-wide. Wrong workgroups come back in the result (``.ok`` False)
+        with the CUs they ran on, not as an exception."""
+        res = _LdsSweepResultC()
+        gbs = ctypes.c_double(0)
+        rc = self.lib.na_lds_sweep(
+            dev, workgroups, ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed),
+            ctypes.byref(res), ctypes.byref(gbs),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            raise NodeAgentError(f"lds_sweep({dev}): {self._err()}")
+        return LdsSweepResult._from_c(res, gbs.value)
+
+    def _run_lds_sweep(self, g: GPUReport) -> None:
+        res = self.lds_sweep(g.index)
+        g.lds_sweep_gbs = round(res.gbs, 1)
+        g.lds_sweep_min_cu_bytes_per_clk = round(res.min_bytes_per_clk, 2)
+        g.lds_sweep_units_seen = res.units_seen
+        g.lds_sweep_bad_workgroups = res.bad_workgroups
+        if res.gbs < MIN_LDS_SWEEP_GBS:
+            g.problems.append(
+                f"LDS sweep {g.lds_sweep_gbs} GB/s below floor {MIN_LDS_SWEEP_GBS}"
+            )
+        if not res.ok:
+            g.problems.append(f"LDS sweep: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         if self.lib.na_p2p_matrix(n, buf) != 0:
@@ -712,7 +927,7 @@ class NodeAgent:
 
     def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
               memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
-              mx_sweep: bool = False) -> NodeReport:
+              mx_sweep: bool = False, lds_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -732,7 +947,13 @@ class NodeAgent:
         that carries the first wrong word. ``mx_sweep`` additionally runs the
         chip-wide sweep on the block-scaled instruction in fp4 and fp6: a
         wrong wave is a problem that names its unit, as is an fp4 rate under
-        ``MIN_MX_SWEEP_TFLOPS``. False (default) calls nothing new."""
+        ``MIN_MX_SWEEP_TFLOPS``. False (default) calls nothing new.
+
+        ``lds_sweep`` additionally runs the chip-wide LDS sweep on every GPU:
+        a wrong workgroup is a problem that names its CU and the phase that
+        failed, as is a stream rate under ``MIN_LDS_SWEEP_GBS``.
+        ``lds_sweep_units_seen`` below the CU count is reported, not a
+        problem. False (default) makes no new library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -772,6 +993,8 @@ class NodeAgent:
                     self._run_mx_checks(g)
                 if mx_sweep:
                     self._run_mx_sweep(g)
+                if lds_sweep:
+                    self._run_lds_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -890,6 +1113,14 @@ def main(argv=None) -> int:
         "attributed to its XCC/SE/SH/CU/SIMD; reports sustained TFLOP/s per format",
     )
     ap.add_argument(
+        "--lds-sweep",
+        action="store_true",
+        help="also run the chip-wide LDS sweep on every GPU: one workgroup at a time on every "
+        "CU through 32/128-bit accesses, LDS-DMA loads at 16/4/12 bytes, the transposed read "
+        "and atomics, every phase checked bit-exactly and a wrong one attributed to its "
+        "XCC/SE/SH/CU; reports the read-stream rate chip-wide and of the slowest CU",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -905,6 +1136,7 @@ def main(argv=None) -> int:
             mfma_sweep=args.mfma_sweep,
             mx_checks=args.mx_checks,
             mx_sweep=args.mx_sweep,
+            lds_sweep=args.lds_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

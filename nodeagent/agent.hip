@@ -12,8 +12,9 @@
 // mfma_frag.h, run and verified by na_mfma_check_run / _verify), an opt-in
 // chip-wide matrix-core sweep (one wave per SIMD of every CU, mfmasweep.h),
 // opt-in single-wave checks and the same sweep on the block-scaled MX
-// instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h), and the
-// xGMI peer-to-peer link matrix.
+// instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h), an
+// opt-in chip-wide LDS sweep (every LDS access path on every CU, ldssweep.h),
+// and the xGMI peer-to-peer link matrix.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
 // consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
@@ -1209,4 +1210,396 @@ extern "C" int na_mx_sweep_verify(const na_mfma_record* recs, long long n, int o
 extern "C" int na_mx_sweep(int dev, int format, int workgroups, int outer,
                            unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
     return ms_sweep(ms_mx, dev, format, workgroups, outer, seed, res, tflops);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide LDS sweep (kernel and specification in ldssweep.h)
+// ---------------------------------------------------------------------------
+//
+// na_lds_selftest above says "N mismatched words" of 32-bit accesses. The
+// sweep runs one workgroup at a time on every CU through every LDS access
+// path (32/128-bit, LDS-DMA at three widths, transposed read, atomics) and a
+// timed read stream, and the host recomputes each workgroup's phase checksums
+// exactly, so a bad LDS is named by (XCC, SE, SH, CU) and phase.
+
+#include "ldssweep.h"
+
+#define NA_LDS_MAX_LISTED 8
+#define NA_LDS_MAX_WORKGROUPS (1 << 20)
+// A pass over 160 KiB is 640 clocks at the LDS's 256 B/clk, 0.27 us at
+// 2.4 GHz: 2^22 passes hold a CU for ~1.1 s at full rate, ~2 s at the half
+// rate a sick CU might run at — NA_MFMA_MAX_OUTER's bound, which keeps a typo
+// from hanging the node.
+#define NA_LDS_MAX_ITERS (1 << 22)
+// 12288 passes x 0.27 us is 3.3 ms per workgroup at full rate, and the
+// default grid puts four workgroups on each CU in turn: at least 13 ms by
+// arithmetic; measured 17.4 ms of stream phase per CU in an 18.3 ms launch
+// (profiles/lds_sweep_mi355x.txt: the loop reaches 195 B/clk) — past the
+// 10 ms from which the in-kernel clock estimate is reliable (see
+// NA_MFMA_DEFAULT_OUTER).
+#define NA_LDS_DEFAULT_ITERS 12288
+
+static const char* const ls_phase_names[LS_PHASES] = {"b32",   "b128", "dma16",  "dma4",
+                                                      "dma12", "tr16", "atomic", "stream"};
+
+typedef struct {
+    uint64_t workgroups, bad_workgroups;
+    uint64_t units_seen, bad_units;   // distinct (xcc, se, sh, cu)
+    uint64_t first_bad_workgroup;     // UINT64_MAX = none
+    // of the first bad workgroup, when its first failing phase compares words
+    // in the kernel; otherwise 0, UINT64_MAX, 0
+    uint64_t bad_words, first_bad_offset, xor_mask;
+    double clock_mhz;                 // median of cycles / realtime x 100 MHz
+    // stream phase, iters * lds_bytes / cycles per workgroup: bytes per
+    // shader clock of the CU it ran on
+    double median_bytes_per_clk, min_bytes_per_clk, max_bytes_per_clk;
+    uint32_t first_bad_unit[4];       // xcc, se, sh, cu
+    uint32_t first_bad_phase;         // LS_* code; LS_PHASES = the record's index
+    uint32_t listed;                  // entries used in bad_list
+    uint32_t bad_list[NA_LDS_MAX_LISTED][4];  // first distinct failing (xcc, se, sh, cu)
+} na_lds_sweep_result;
+
+// Per 1 KiB chunk of each pattern, the sums the checksums are linear in.
+// They do not depend on the workgroup, whose rotation only selects which
+// chunk's sums enter at which step: computed once per (seed, lds_bytes), they
+// make the reference of a workgroup a few hundred multiplications.
+struct ls_sums {
+    uint32_t C;
+    std::vector<uint64_t> s32[2], lo[2], hi[2];  // b32 and b128 at both polarities
+    std::vector<uint64_t> dma_lo, dma_hi, dma_w2, dma_w3, tr, atomic;
+    uint64_t stream_total;
+
+    static void words(uint64_t base, int pat, uint32_t pol, uint32_t chunk, uint32_t* w) {
+        for (uint32_t i = 0; i < LS_CHUNK_WORDS; ++i)
+            w[i] = ls_pat(base, pat, chunk * LS_CHUNK_WORDS + i) ^ pol;
+    }
+    static uint64_t sum32(const uint32_t* w) {
+        uint64_t s = 0;
+        for (uint32_t i = 0; i < LS_CHUNK_WORDS; ++i) s += w[i];
+        return s;
+    }
+    static void sum128(const uint32_t* w, uint64_t* lo, uint64_t* hi) {
+        *lo = *hi = 0;
+        for (uint32_t i = 0; i < LS_CHUNK_WORDS; i += 4) {
+            *lo += (uint64_t)w[i] | ((uint64_t)w[i + 1] << 32);
+            *hi += (uint64_t)w[i + 2] | ((uint64_t)w[i + 3] << 32);
+        }
+    }
+
+    ls_sums(uint64_t base, uint32_t lds_bytes) : C(lds_bytes / 1024), stream_total(0) {
+        uint32_t w[LS_CHUNK_WORDS];
+        for (int p = 0; p < 2; ++p) s32[p].resize(C), lo[p].resize(C), hi[p].resize(C);
+        dma_lo.resize(C), dma_hi.resize(C), dma_w2.resize(C), dma_w3.resize(C);
+        tr.resize(C), atomic.resize(C);
+        for (uint32_t c = 0; c < C; ++c) {
+            for (int p = 0; p < 2; ++p) {
+                words(base, LS_PAT_B32, p ? ~0u : 0u, c, w);
+                s32[p][c] = sum32(w);
+                words(base, LS_PAT_B128, p ? ~0u : 0u, c, w);
+                sum128(w, &lo[p][c], &hi[p][c]);
+            }
+            words(base, LS_PAT_DMA, 0, c, w);
+            sum128(w, &dma_lo[c], &dma_hi[c]);
+            dma_w2[c] = dma_w3[c] = 0;
+            for (uint32_t i = 0; i < LS_CHUNK_WORDS; i += 4) dma_w2[c] += w[i + 2], dma_w3[c] += w[i + 3];
+            // a tile is 32 words, row q its words 8q..8q+7; column i of row
+            // q lands in bits 16q.. of lane i's value
+            words(base, LS_PAT_TR16, 0, c, w);
+            tr[c] = 0;
+            for (uint32_t i = 0; i < LS_CHUNK_WORDS; ++i)
+                tr[c] += ((uint64_t)(w[i] & 0xFFFF) + (uint64_t)(w[i] >> 16)) << (16 * ((i >> 3) & 3));
+            words(base, LS_PAT_ATOMIC, 0, c, w);
+            atomic[c] = 0;
+            for (uint32_t i = 0; i < LS_CHUNK_WORDS; ++i) atomic[c] += (uint32_t)(w[i] + (w[i] >> 16));
+            words(base, LS_PAT_STREAM, 0, c, w);
+            uint64_t l, h;
+            sum128(w, &l, &h);
+            stream_total += l + h;
+        }
+    }
+
+    // What 256 threads folding c = c*G + value leave in sum: Horner over the
+    // per-step sums of the values.
+    static void fold(uint64_t& c, uint64_t step_sum) { c = c * MS_G + step_sum; }
+
+    void fold32(uint64_t& c, const std::vector<uint64_t>& s, uint32_t rot, uint32_t chunks) const {
+        for (uint32_t k = 0; k < chunks; ++k) fold(c, s[(k + rot) % C]);
+    }
+    void fold128(uint64_t& c, const std::vector<uint64_t>& l, const std::vector<uint64_t>& h,
+                 uint32_t rot) const {
+        for (uint32_t k = 0; k < C / 4; ++k) {
+            uint64_t sl = 0, sh = 0;
+            for (uint32_t m = 0; m < 4; ++m) sl += l[(4 * k + m + rot) % C], sh += h[(4 * k + m + rot) % C];
+            fold(c, sl);
+            fold(c, sh);
+        }
+    }
+
+    void expected(uint64_t workgroup, int iters, uint64_t* out) const {
+        const uint32_t rot = (uint32_t)(workgroup % C);
+        for (int p = 0; p < LS_PHASES; ++p) out[p] = 0;
+        for (int p = 0; p < 2; ++p) fold32(out[LS_B32], s32[p], rot, C);
+        for (int p = 0; p < 2; ++p) fold128(out[LS_B128], lo[p], hi[p], rot);
+        fold128(out[LS_DMA16], dma_lo, dma_hi, rot);
+        fold128(out[LS_DMA4], dma_lo, dma_hi, (rot + 1) % C);
+        // dma12 renews three words of every vector; the fourth is still dma4's
+        for (uint32_t k = 0; k < C / 4; ++k) {
+            uint64_t sl = 0, sh = 0;
+            for (uint32_t m = 0; m < 4; ++m) {
+                const uint32_t c12 = (4 * k + m + rot + 2) % C, c4 = (4 * k + m + rot + 1) % C;
+                sl += dma_lo[c12];
+                sh += dma_w2[c12] + (dma_w3[c4] << 32);
+            }
+            fold(out[LS_DMA12], sl);
+            fold(out[LS_DMA12], sh);
+        }
+        for (uint32_t k = 0; k < C / 2; ++k)
+            fold(out[LS_TR16], tr[(2 * k + rot) % C] + tr[(2 * k + 1 + rot) % C]);
+        fold32(out[LS_ATOMIC], atomic, rot, C);
+        out[LS_STREAM] = (uint64_t)iters * stream_total;
+    }
+};
+
+static bool ls_bytes_ok(long long lds_bytes) {
+    return lds_bytes >= LS_GRANULE && lds_bytes <= LS_MAX_BYTES && lds_bytes % LS_GRANULE == 0;
+}
+
+// The per-workgroup LDS allocation the sweep launches with and, at
+// lds_bytes 0, tests: sharedMemPerBlock, capped at 160 KiB and rounded down
+// to the sweep's granule.
+extern "C" int na_lds_sweep_allocation(int dev, long long* bytes) {
+    if (bytes == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_lds_sweep_allocation: need a result pointer");
+        return NA_ERR_ARG;
+    }
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    size_t alloc = prop.sharedMemPerBlock;
+    if (alloc > LS_MAX_BYTES) alloc = LS_MAX_BYTES;
+    *bytes = (long long)(alloc / LS_GRANULE * LS_GRANULE);
+    return NA_OK;
+}
+
+// Pure host code: the LS_PHASES checksums of one workgroup, in the order of
+// the LS_* codes. lds_bytes is explicit here (a multiple of 4096 in
+// 4096..160 KiB); n is the room in `checksums`.
+extern "C" int na_lds_sweep_expected(unsigned long long seed, unsigned long long workgroup,
+                                     long long lds_bytes, int iters, uint64_t* checksums, int n) {
+    if (!ls_bytes_ok(lds_bytes) || iters < 1 || checksums == nullptr || n < LS_PHASES) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_lds_sweep_expected: need lds_bytes a multiple of %d in %d..%d (got "
+                      "%lld), iters >= 1 (got %d) and room for %d checksums (n %d)",
+                      LS_GRANULE, LS_GRANULE, LS_MAX_BYTES, lds_bytes, iters, LS_PHASES, n);
+        return NA_ERR_ARG;
+    }
+    ls_sums(seed * MS_G, (uint32_t)lds_bytes).expected(workgroup, iters, checksums);
+    return NA_OK;
+}
+
+// One launch of `workgroups` workgroups, HIP-event timed; out receives one
+// record per workgroup. lds_bytes 0 = the whole allocation. Argument errors
+// are detected before any HIP call.
+extern "C" int na_lds_sweep_run(int dev, int workgroups, long long lds_bytes, int iters,
+                                unsigned long long seed, na_lds_record* out, long long n_out,
+                                double* ms) {
+    if (workgroups < 1 || workgroups > NA_LDS_MAX_WORKGROUPS ||
+        (lds_bytes != 0 && !ls_bytes_ok(lds_bytes)) || iters < 1 || iters > NA_LDS_MAX_ITERS ||
+        out == nullptr || n_out < (long long)workgroups) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_lds_sweep_run: need workgroups in 1..%d (got %d), lds_bytes 0 or a "
+                      "multiple of %d up to %d (got %lld), iters in 1..%d (got %d) and room for "
+                      "a record per workgroup (out %p, n_out %lld)",
+                      NA_LDS_MAX_WORKGROUPS, workgroups, LS_GRANULE, LS_MAX_BYTES, lds_bytes,
+                      NA_LDS_MAX_ITERS, iters, (void*)out, n_out);
+        return NA_ERR_ARG;
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    long long alloc = 0;
+    int rc = na_lds_sweep_allocation(dev, &alloc);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes == 0) lds_bytes = alloc;
+    if (lds_bytes > alloc || alloc < LS_GRANULE) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_lds_sweep_run: lds_bytes %lld exceeds the device's %lld-byte "
+                      "per-workgroup LDS allocation",
+                      lds_bytes, alloc);
+        return NA_ERR_ARG;
+    }
+    // the dma phases' source: pattern LS_PAT_DMA
+    const uint32_t W = (uint32_t)lds_bytes / 4;
+    const mt_u64 base = seed * MS_G;
+    std::vector<uint32_t> pattern(W);
+    for (uint32_t j = 0; j < W; ++j) pattern[j] = ls_pat(base, LS_PAT_DMA, j);
+    dev_buf<uint32_t> src;
+    HIP_CHECK(src.alloc(pattern.size()));
+    HIP_CHECK(hipMemcpy(src.p, pattern.data(), pattern.size() * sizeof(uint32_t),
+                        hipMemcpyHostToDevice));
+    const size_t n = (size_t)workgroups;
+    dev_buf<na_lds_record> d;
+    HIP_CHECK(d.alloc(n));
+    // a record its workgroup never wrote carries no valid index and fails the verify
+    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(na_lds_record)));
+    dev_events<2> ev;
+    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(ev.e[0]));
+    // the whole allocation whatever lds_bytes is: one workgroup per CU
+    lds_sweep_kernel<<<dim3((unsigned)workgroups), dim3(LS_BLOCK), (size_t)alloc>>>(
+        d.p, src.p, base, (uint32_t)lds_bytes, iters);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[1]));
+    HIP_CHECK(hipEventSynchronize(ev.e[1]));
+    float elapsed = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(na_lds_record), hipMemcpyDeviceToHost));
+    if (ms) *ms = (double)elapsed;
+    return NA_OK;
+}
+
+static inline uint32_t ls_cu_key(const na_lds_record& r) {
+    return ((r.xcc & 15) << 7) | ((r.se & 3) << 5) | ((r.sh & 1) << 4) | (r.cu & 15);
+}
+
+static double ls_median(std::vector<double>& v) {
+    if (v.empty()) return 0.0;
+    std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
+    return v[v.size() / 2];
+}
+
+// Pure host code: record i is workgroup i. A workgroup is bad when a phase
+// checksum is not the expected one, when it does not carry its own index, or
+// when its in-kernel count of bad words is not zero. Returns NA_ERR_VERIFY on
+// any bad workgroup; *res is filled either way.
+extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long long lds_bytes,
+                                   int iters, unsigned long long seed, na_lds_sweep_result* res) {
+    if (recs == nullptr || n < 1 || !ls_bytes_ok(lds_bytes) || iters < 1 || res == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_lds_sweep_verify: need records, n >= 1 (got %lld), lds_bytes a "
+                      "multiple of %d in %d..%d (got %lld), iters >= 1 (got %d) and a result "
+                      "pointer",
+                      n, LS_GRANULE, LS_GRANULE, LS_MAX_BYTES, lds_bytes, iters);
+        return NA_ERR_ARG;
+    }
+    std::memset(res, 0, sizeof(*res));
+    res->workgroups = (uint64_t)n;
+    res->first_bad_workgroup = res->first_bad_offset = UINT64_MAX;
+    res->first_bad_phase = ~0u;
+    const ls_sums sums(seed * MS_G, (uint32_t)lds_bytes);
+    // every C-th workgroup shares a rotation, hence its checksums
+    std::vector<uint64_t> want((size_t)sums.C * LS_PHASES);
+    for (uint32_t r = 0; r < sums.C; ++r) sums.expected(r, iters, &want[(size_t)r * LS_PHASES]);
+    std::vector<bool> seen(1 << 11, false), bad(1 << 11, false);
+    std::vector<double> mhz, rate;
+    mhz.reserve((size_t)n), rate.reserve((size_t)n);
+    double min_rate = 0.0, max_rate = 0.0;
+    for (long long i = 0; i < n; ++i) {
+        const na_lds_record& r = recs[i];
+        const uint32_t key = ls_cu_key(r);
+        if (!seen[key]) {
+            seen[key] = true;
+            res->units_seen++;
+        }
+        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
+        if (r.cycles) {
+            const double b = (double)iters * (double)lds_bytes / (double)r.cycles;
+            if (rate.empty() || b < min_rate) min_rate = b;
+            if (b > max_rate) max_rate = b;
+            rate.push_back(b);
+        }
+        const uint64_t* w = &want[(size_t)(i % sums.C) * LS_PHASES];
+        uint32_t phase = 0;
+        while (phase < LS_PHASES && r.checksum[phase] == w[phase]) ++phase;
+        if (phase == LS_PHASES && r.bad_words != 0)
+            phase = r.bad_phase < LS_PHASES ? r.bad_phase : (uint32_t)LS_B32;
+        if (phase == LS_PHASES && r.workgroup == (uint64_t)i) continue;
+        // `phase` failed; LS_PHASES: the record is only in the wrong place
+        res->bad_workgroups++;
+        if (!bad[key]) {
+            bad[key] = true;
+            res->bad_units++;
+        }
+        const uint32_t unit[4] = {r.xcc, r.se, r.sh, r.cu};
+        if (res->first_bad_workgroup == UINT64_MAX) {
+            res->first_bad_workgroup = (uint64_t)i;
+            res->first_bad_phase = phase;
+            std::memcpy(res->first_bad_unit, unit, sizeof(unit));
+            if (r.bad_words != 0 && r.bad_phase == phase) {
+                res->bad_words = r.bad_words;
+                res->first_bad_offset = r.first_bad_offset;
+                res->xor_mask = r.xor_mask;
+            }
+        }
+        bool listed = false;
+        for (uint32_t k = 0; k < res->listed && !listed; ++k)
+            listed = std::memcmp(res->bad_list[k], unit, sizeof(unit)) == 0;
+        if (!listed && res->listed < NA_LDS_MAX_LISTED)
+            std::memcpy(res->bad_list[res->listed++], unit, sizeof(unit));
+    }
+    res->clock_mhz = ls_median(mhz);
+    res->median_bytes_per_clk = ls_median(rate);
+    res->min_bytes_per_clk = min_rate;
+    res->max_bytes_per_clk = max_rate;
+    if (res->bad_workgroups == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    char where[128] = "";
+    if (res->first_bad_offset != UINT64_MAX)
+        std::snprintf(where, sizeof(where),
+                      ", %llu bad words, first at LDS offset 0x%llx (bank %llu), failing bits "
+                      "0x%08llx",
+                      (unsigned long long)res->bad_words,
+                      (unsigned long long)res->first_bad_offset,
+                      (unsigned long long)(res->first_bad_offset / 4 % 64),
+                      (unsigned long long)res->xor_mask);
+    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                  "lds sweep: %llu of %llu workgroups wrong on %llu CU(s), first workgroup %llu "
+                  "in phase %s on xcc%u.se%u.sh%u.cu%u%s",
+                  (unsigned long long)res->bad_workgroups, (unsigned long long)res->workgroups,
+                  (unsigned long long)res->bad_units,
+                  (unsigned long long)res->first_bad_workgroup,
+                  res->first_bad_phase < LS_PHASES ? ls_phase_names[res->first_bad_phase] : "index",
+                  u[0], u[1], u[2], u[3], where);
+    return NA_ERR_VERIFY;
+}
+
+// Whole sweep: one untimed warm-up launch, the timed launch, the verify.
+// workgroups 0 = 4 per CU, lds_bytes 0 = the whole allocation, iters 0 =
+// NA_LDS_DEFAULT_ITERS. *gbs is the chip-wide rate of the stream phase from
+// the in-kernel stamps alone, not the launch's event time (which includes
+// the other phases):
+//   gbs = median_bytes_per_clk x units_seen x clock_mhz / 1000
+// i.e. the median CU's bytes per shader clock, on every CU that took part, at
+// the median measured clock.
+extern "C" int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int iters,
+                            unsigned long long seed, na_lds_sweep_result* res, double* gbs) {
+    if (res == nullptr || workgroups < 0 || workgroups > NA_LDS_MAX_WORKGROUPS ||
+        (lds_bytes != 0 && !ls_bytes_ok(lds_bytes)) || iters < 0 || iters > NA_LDS_MAX_ITERS) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_lds_sweep: need workgroups in 0..%d (got %d), lds_bytes 0 or a "
+                      "multiple of %d up to %d (got %lld), iters in 0..%d (got %d) and a result "
+                      "pointer",
+                      NA_LDS_MAX_WORKGROUPS, workgroups, LS_GRANULE, LS_MAX_BYTES, lds_bytes,
+                      NA_LDS_MAX_ITERS, iters);
+        return NA_ERR_ARG;
+    }
+    if (iters == 0) iters = NA_LDS_DEFAULT_ITERS;
+    if (workgroups == 0) {
+        hipDeviceProp_t prop;
+        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+        workgroups = 4 * prop.multiProcessorCount;
+    }
+    if (lds_bytes == 0) {
+        int rc = na_lds_sweep_allocation(dev, &lds_bytes);
+        if (rc != NA_OK) return rc;
+    }
+    std::vector<na_lds_record> recs((size_t)workgroups);
+    double ms = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
+        int rc = na_lds_sweep_run(dev, workgroups, lds_bytes, iters, seed, recs.data(),
+                                  (long long)recs.size(), &ms);
+        if (rc != NA_OK) return rc;
+    }
+    int rc = na_lds_sweep_verify(recs.data(), (long long)recs.size(), lds_bytes, iters, seed, res);
+    if (gbs && (rc == NA_OK || rc == NA_ERR_VERIFY))
+        *gbs = res->median_bytes_per_clk * (double)res->units_seen * res->clock_mhz / 1000.0;
+    return rc;
 }
