@@ -6,7 +6,8 @@ evidence. Fails LOUDLY if the native library is missing on a GPU machine —
 there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
-[--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]``
+[--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
+[--valu-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -108,6 +109,28 @@ NO_BAD_WORKGROUP = (1 << 64) - 1
 # loops has not been measured; 0.70 is borrowed from the MFMA floor above.
 # 0 disables the floor.
 MIN_LDS_SWEEP_GBS = 82464.4
+
+# Chip-wide vector-unit sweep (nodeagent/valusweep.h). The default seed is
+# "MI355XVS"; a record carries one checksum per phase, in this order. A listed
+# wave's phase mask has two more bits: the record's own index and the
+# placement of its workgroup.
+DEFAULT_VALU_SWEEP_SEED = 0x4D493335_35585653
+VALU_SWEEP_PHASES = ("rf", "rf_inv", "i32", "f32", "f64", "pk", "xlane", "trans", "stream")
+VALU_SWEEP_MASK_NAMES = VALU_SWEEP_PHASES + ("index", "placement")
+VALU_SWEEP_FIRST_VGPR = 32  # v0..v31 hold the test's own state and are not pattern-tested
+VALU_SWEEP_MAX_ITERS = ((1 << 24) - 2048) // 2 - 1  # the stream phase is exact up to here
+VALU_SWEEP_MAX_LISTED = 8
+VALU_SWEEP_XLANE_MOVES = 8
+NO_BAD_SLOT = (1 << 32) - 1
+# FLOP per clock of one SIMD at the vector f32 peak (157.3 TFLOP/s over 1024
+# SIMDs at 2.4 GHz): a ceiling, no floor
+VALU_SWEEP_PEAK_FLOP_PER_CLK = 64
+# Floor of the default sweep's chip-wide stream rate: 0.70 x the 108.72
+# TFLOP/s median of five processes on MI355X
+# (profiles/valu_sweep_mi355x.txt; 51.2 of the 64 FLOP per clock and SIMD).
+# The device-to-device spread of VALU loops has not been measured; 0.70 is
+# borrowed from the MFMA floor above. 0 disables the floor.
+MIN_VALU_SWEEP_TFLOPS = 76.1
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -350,6 +373,122 @@ class LdsSweepResult:
         )
 
 
+class ValuRecord(ctypes.Structure):
+    """One wave of the vector-unit sweep (``na_valu_record``): a checksum per
+    phase of ``VALU_SWEEP_PHASES``, the s_memtime / s_memrealtime deltas around
+    the stream phase, its global wave index, the unit it ran on, and the
+    kernel's own diagnosis of the register-file phases (count of wrong
+    registers, slot and lane of the first, OR of got^want)."""
+
+    _fields_ = [
+        ("checksum", ctypes.c_uint64 * len(VALU_SWEEP_PHASES)),
+        ("cycles", ctypes.c_uint64),
+        ("realtime", ctypes.c_uint64),
+        ("wave", ctypes.c_uint32),
+        ("xcc", ctypes.c_uint32),
+        ("se", ctypes.c_uint32),
+        ("sh", ctypes.c_uint32),
+        ("cu", ctypes.c_uint32),
+        ("simd", ctypes.c_uint32),
+        ("rf_bad", ctypes.c_uint32),
+        ("rf_first_slot", ctypes.c_uint32),
+        ("rf_first_lane", ctypes.c_uint32),
+        ("rf_xor", ctypes.c_uint32),
+    ]
+
+
+class _ValuSweepResultC(ctypes.Structure):
+    _fields_ = [
+        ("waves", ctypes.c_uint64),
+        ("bad_waves", ctypes.c_uint64),
+        ("cus_seen", ctypes.c_uint64),
+        ("simds_seen", ctypes.c_uint64),
+        ("trans_unchecked", ctypes.c_uint64),
+        ("trans_consensus", ctypes.c_uint64),
+        ("median_cycles", ctypes.c_uint64),
+        ("clock_mhz", ctypes.c_double),
+        ("median_flop_per_clk", ctypes.c_double),
+        ("min_flop_per_clk", ctypes.c_double),
+        ("tflops", ctypes.c_double),
+        ("rf_bad", ctypes.c_uint32),
+        ("rf_first_slot", ctypes.c_uint32),
+        ("rf_first_lane", ctypes.c_uint32),
+        ("rf_xor", ctypes.c_uint32),
+        ("listed", ctypes.c_uint32),
+        ("bad_list", (ctypes.c_uint32 * 7) * VALU_SWEEP_MAX_LISTED),
+    ]
+
+
+def valu_slot_name(slot: int) -> str:
+    """Register of register-file slot ``slot``: ``a0..a255``, then
+    ``v32..v255``; slots from 512 are the same registers in the inverted
+    phase."""
+    slot &= 511
+    return f"a{slot}" if slot < 256 else f"v{slot - 256 + VALU_SWEEP_FIRST_VGPR}"
+
+
+@dataclass
+class ValuSweepResult:
+    """Outcome of a vector-unit sweep verify. ``bad`` lists the first bad
+    waves (at most ``VALU_SWEEP_MAX_LISTED``) as ``(wave, (xcc, se, sh, cu,
+    simd), [names of the phases that failed])``; ``bad_waves`` is the full
+    count. ``trans_unchecked`` says the transcendental phase, which is checked
+    by consensus among the records, had fewer than 3 records or no strict
+    majority: not a failure. The ``rf_*`` fields are the kernel's own
+    diagnosis of the first bad wave when it failed a register-file phase.
+    The rates are the stream phase's FLOP per shader clock and SIMD;
+    ``tflops`` comes from the in-kernel stamps, never from launch time."""
+
+    waves: int = 0
+    bad_waves: int = 0
+    cus_seen: int = 0
+    simds_seen: int = 0
+    trans_unchecked: bool = True
+    trans_consensus: int = 0
+    median_cycles: int = 0
+    clock_mhz: float = 0.0
+    median_flop_per_clk: float = 0.0
+    min_flop_per_clk: float = 0.0
+    tflops: float = 0.0
+    rf_bad: int = 0
+    rf_first_slot: int = NO_BAD_SLOT
+    rf_first_lane: int = NO_BAD_SLOT
+    rf_xor: int = 0
+    bad: list = field(default_factory=list)
+
+    @property
+    def ok(self) -> bool:
+        return self.bad_waves == 0
+
+    def describe(self) -> str:
+        names = ", ".join(
+            f"{mfma_unit_name(unit)} ({','.join(phases)})" for _wave, unit, phases in self.bad
+        )
+        more = ", ..." if self.bad_waves > len(self.bad) else ""
+        where = ""
+        if self.rf_bad:
+            where = (
+                f"; first: {self.rf_bad} wrong registers, first {valu_slot_name(self.rf_first_slot)}"
+                f"{' inverted' if self.rf_first_slot >= 512 else ''} lane {self.rf_first_lane}, "
+                f"failing bits {self.rf_xor:#010x}"
+            )
+        return f"{self.bad_waves} of {self.waves} waves wrong: {names}{more}{where}"
+
+    @classmethod
+    def _from_c(cls, res: "_ValuSweepResultC"):
+        bad = []
+        for i in range(res.listed):
+            row = list(res.bad_list[i])
+            phases = [n for p, n in enumerate(VALU_SWEEP_MASK_NAMES) if row[6] >> p & 1]
+            bad.append((row[0], tuple(row[1:6]), phases))
+        return cls(
+            res.waves, res.bad_waves, res.cus_seen, res.simds_seen, bool(res.trans_unchecked),
+            res.trans_consensus, res.median_cycles, res.clock_mhz, res.median_flop_per_clk,
+            res.min_flop_per_clk, res.tflops, res.rf_bad, res.rf_first_slot, res.rf_first_lane,
+            res.rf_xor, bad,
+        )
+
+
 def _load_lib() -> ctypes.CDLL:
     for p in _SEARCH_PATHS:
         if os.path.exists(p):
@@ -379,6 +518,12 @@ class GPUReport:
     lds_sweep_min_cu_bytes_per_clk: float = 0.0
     lds_sweep_units_seen: int = 0
     lds_sweep_bad_workgroups: int = 0
+    # chip-wide vector-unit sweep (opt-in; all "not run" by default)
+    valu_sweep_tflops: float = 0.0
+    valu_sweep_min_simd_flop_per_clk: float = 0.0
+    valu_sweep_simds_seen: int = 0
+    valu_sweep_bad_waves: int = 0
+    valu_sweep_trans_unchecked: bool = False
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -908,6 +1053,98 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"LDS sweep: {res.describe()}")
 
+    # -- chip-wide vector-unit sweep ---------------------------------------------
+
+    def valu_sweep_slots(self) -> int:
+        """Registers per lane the register-file phases pattern-test."""
+        return self.lib.na_valu_sweep_slots()
+
+    def valu_sweep_xlane_table(self, move: int) -> list:
+        """Source slot of every destination slot under cross-lane move
+        ``move`` of the xlane phase, as the host reference models it: 64
+        lanes, or for the two swaps 128 (A's lanes, then B's). Needs no GPU."""
+        out = (ctypes.c_int * 128)()
+        n = self.lib.na_valu_sweep_xlane_table(move, out, len(out))
+        if n < 0:
+            raise NodeAgentError(f"valu_sweep_xlane_table: {self._err()}")
+        return list(out[:n])
+
+    def valu_sweep_expected(self, wave: int, iters: int,
+                            seed: int = DEFAULT_VALU_SWEEP_SEED) -> list:
+        """The checksums wave ``wave`` must report, one per phase of
+        ``VALU_SWEEP_PHASES``, with ``iters`` stream rounds; the ``trans``
+        entry, which has no host reference, is 0 (host arithmetic only; needs
+        no GPU)."""
+        out = (ctypes.c_uint64 * len(VALU_SWEEP_PHASES))()
+        rc = self.lib.na_valu_sweep_expected(
+            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), iters, out
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"valu_sweep_expected: {self._err()}")
+        return list(out)
+
+    def valu_sweep_run(self, dev: int, workgroups: int = 1, iters: int = 1,
+                       seed: int = DEFAULT_VALU_SWEEP_SEED) -> tuple:
+        """One launch of ``workgroups`` x 4 waves, each through every phase
+        with ``iters`` stream rounds. Returns ``(records, ms)``: a ctypes
+        array of ``ValuRecord`` (record i is wave i) and the HIP-event time."""
+        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
+        recs = (ValuRecord * max(n, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_valu_sweep_run(
+            dev, workgroups, iters, ctypes.c_ulonglong(seed), recs, ctypes.c_longlong(n),
+            ctypes.byref(ms),
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"valu_sweep_run({dev}): {self._err()}")
+        return recs, ms.value
+
+    def valu_sweep_verify(self, recs, iters: int, seed: int = DEFAULT_VALU_SWEEP_SEED) -> tuple:
+        """Compare every record against the host reference and, for the
+        transcendental phase, against the other records. Returns ``(rc,
+        ValuSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad wave, and
+        ``na_last_error`` then names the first failing unit and phase."""
+        res = _ValuSweepResultC()
+        rc = self.lib.na_valu_sweep_verify(
+            recs, ctypes.c_longlong(len(recs)), iters, ctypes.c_ulonglong(seed), ctypes.byref(res)
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, ValuSweepResult()
+        return rc, ValuSweepResult._from_c(res)
+
+    def valu_sweep(self, dev: int, workgroups: int = 0, iters: int = 0,
+                   seed: int = DEFAULT_VALU_SWEEP_SEED) -> ValuSweepResult:
+        """Run one wave per SIMD on every CU through the vector unit: a
+        pattern over 480 of the 512 registers per lane at both polarities,
+        integer, f32, f64, packed-f32/f16, cross-lane and transcendental
+        chains, and a timed packed-f32 stream (``workgroups`` 0 = 4 per CU,
+        ``iters`` 0 = the default round count). Every exact phase of every
+        wave is verified bit for bit against the host reference, the
+        transcendental phase by consensus among the SIMDs (a fault common to
+        the whole chip passes it). Wrong waves come back in the result
+        (``.ok`` False) with the SIMDs they ran on, not as an exception."""
+        res = _ValuSweepResultC()
+        rc = self.lib.na_valu_sweep(
+            dev, workgroups, iters, ctypes.c_ulonglong(seed), ctypes.byref(res)
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            raise NodeAgentError(f"valu_sweep({dev}): {self._err()}")
+        return ValuSweepResult._from_c(res)
+
+    def _run_valu_sweep(self, g: GPUReport) -> None:
+        res = self.valu_sweep(g.index)
+        g.valu_sweep_tflops = round(res.tflops, 1)
+        g.valu_sweep_min_simd_flop_per_clk = round(res.min_flop_per_clk, 2)
+        g.valu_sweep_simds_seen = res.simds_seen
+        g.valu_sweep_bad_waves = res.bad_waves
+        g.valu_sweep_trans_unchecked = res.trans_unchecked
+        if res.tflops < MIN_VALU_SWEEP_TFLOPS:
+            g.problems.append(
+                f"VALU sweep {g.valu_sweep_tflops} TFLOP/s below floor {MIN_VALU_SWEEP_TFLOPS}"
+            )
+        if not res.ok:
+            g.problems.append(f"VALU sweep: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         if self.lib.na_p2p_matrix(n, buf) != 0:
@@ -927,7 +1164,8 @@ class NodeAgent:
 
     def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
               memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
-              mx_sweep: bool = False, lds_sweep: bool = False) -> NodeReport:
+              mx_sweep: bool = False, lds_sweep: bool = False,
+              valu_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -953,7 +1191,14 @@ class NodeAgent:
         a wrong workgroup is a problem that names its CU and the phase that
         failed, as is a stream rate under ``MIN_LDS_SWEEP_GBS``.
         ``lds_sweep_units_seen`` below the CU count is reported, not a
-        problem. False (default) makes no new library call."""
+        problem. False (default) makes no new library call.
+
+        ``valu_sweep`` additionally runs the chip-wide vector-unit sweep on
+        every GPU: a wrong wave is a problem that names its SIMD and the
+        phases that failed, as is a stream rate under
+        ``MIN_VALU_SWEEP_TFLOPS``. ``valu_sweep_simds_seen`` below 4 x the CU
+        count and ``valu_sweep_trans_unchecked`` are reported, not problems.
+        False (default) makes no new library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -995,6 +1240,8 @@ class NodeAgent:
                     self._run_mx_sweep(g)
                 if lds_sweep:
                     self._run_lds_sweep(g)
+                if valu_sweep:
+                    self._run_valu_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -1121,6 +1368,15 @@ def main(argv=None) -> int:
         "XCC/SE/SH/CU; reports the read-stream rate chip-wide and of the slowest CU",
     )
     ap.add_argument(
+        "--valu-sweep",
+        action="store_true",
+        help="also run the chip-wide vector-unit sweep on every GPU: one wave per SIMD of "
+        "every CU through a register-file pattern (480 of 512 registers per lane, both "
+        "polarities), integer, f32, f64, packed, cross-lane and transcendental chains, every "
+        "exact phase checked bit for bit and a wrong one attributed to its "
+        "XCC/SE/SH/CU/SIMD; reports the packed-f32 stream rate chip-wide and of the slowest SIMD",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -1137,6 +1393,7 @@ def main(argv=None) -> int:
             mx_checks=args.mx_checks,
             mx_sweep=args.mx_sweep,
             lds_sweep=args.lds_sweep,
+            valu_sweep=args.valu_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

@@ -14,7 +14,8 @@
 // opt-in single-wave checks and the same sweep on the block-scaled MX
 // instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h), an
 // opt-in chip-wide LDS sweep (every LDS access path on every CU, ldssweep.h),
-// and the xGMI peer-to-peer link matrix.
+// an opt-in chip-wide vector-unit sweep (register file and VALU of every
+// SIMD, valusweep.h), and the xGMI peer-to-peer link matrix.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
 // consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
@@ -1076,7 +1077,9 @@ static int ms_run(const ms_family& fam, int dev, int code, int workgroups, int o
     return NA_OK;
 }
 
-static inline uint32_t ms_cu_key(const na_mfma_record& r) {
+// any of the sweeps' record types
+template <typename R>
+static inline uint32_t ms_cu_key(const R& r) {
     return ((r.xcc & 15) << 7) | ((r.se & 3) << 5) | ((r.sh & 1) << 4) | (r.cu & 15);
 }
 
@@ -1456,10 +1459,6 @@ extern "C" int na_lds_sweep_run(int dev, int workgroups, long long lds_bytes, in
     return NA_OK;
 }
 
-static inline uint32_t ls_cu_key(const na_lds_record& r) {
-    return ((r.xcc & 15) << 7) | ((r.se & 3) << 5) | ((r.sh & 1) << 4) | (r.cu & 15);
-}
-
 static double ls_median(std::vector<double>& v) {
     if (v.empty()) return 0.0;
     std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
@@ -1494,7 +1493,7 @@ extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long 
     double min_rate = 0.0, max_rate = 0.0;
     for (long long i = 0; i < n; ++i) {
         const na_lds_record& r = recs[i];
-        const uint32_t key = ls_cu_key(r);
+        const uint32_t key = ms_cu_key(r);
         if (!seen[key]) {
             seen[key] = true;
             res->units_seen++;
@@ -1602,4 +1601,406 @@ extern "C" int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int it
     if (gbs && (rc == NA_OK || rc == NA_ERR_VERIFY))
         *gbs = res->median_bytes_per_clk * (double)res->units_seen * res->clock_mhz / 1000.0;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide vector-unit sweep (kernel and specification in valusweep.h)
+// ---------------------------------------------------------------------------
+//
+// na_fma_selftest above is one short f32 chain whose mismatches go into one
+// counter. The sweep runs one wave per SIMD on every CU through a
+// register-file pattern at both polarities, integer, f32, f64, packed,
+// cross-lane and transcendental chains and a timed packed-f32 stream, and the
+// host recomputes every exact checksum, so a bad SIMD is named by (XCC, SE,
+// SH, CU, SIMD) and phase. The transcendental phase has no exact reference:
+// there the records are compared with each other.
+
+#include "valusweep.h"
+
+#define NA_VALU_MAX_LISTED 8
+#define NA_VALU_MAX_WORKGROUPS (1 << 20)
+// Bits of a listed wave's phase mask above the VS_PHASES checksum bits: the
+// record does not carry its own index (a missing or duplicated wave), or the
+// four waves of its workgroup do not sit on four SIMDs of one CU.
+#define NA_VALU_BAD_INDEX (1u << VS_PHASES)
+#define NA_VALU_BAD_PLACEMENT (1u << (VS_PHASES + 1))
+// 131072 rounds x 16 v_pk_fma_f32 at the measured 5 clocks per instruction is
+// 10.5 M clocks per workgroup, ~4.5 ms, and the default grid puts four
+// workgroups on each CU in turn: 18.8 ms per launch measured
+// (profiles/valu_sweep_mi355x.txt) — past the 10 ms from which the in-kernel
+// clock estimate is reliable (see NA_MFMA_DEFAULT_OUTER).
+#define NA_VALU_DEFAULT_ITERS 131072
+
+typedef struct {
+    uint64_t waves, bad_waves;
+    uint64_t cus_seen, simds_seen;  // distinct (xcc, se, sh, cu) and (.., simd)
+    uint64_t trans_unchecked;       // 1: fewer than 3 records or no strict majority
+    uint64_t trans_consensus;       // the majority's trans checksum; 0 when unchecked
+    uint64_t median_cycles;         // of the stream phase
+    double clock_mhz;               // median of cycles / realtime x 100 MHz
+    // stream phase, FLOP per shader clock of the SIMD the wave ran on
+    double median_flop_per_clk, min_flop_per_clk;
+    double tflops;  // median_flop_per_clk x simds_seen x clock_mhz / 1e6
+    // the first listed wave's in-kernel register-file diagnosis
+    uint32_t rf_bad, rf_first_slot, rf_first_lane, rf_xor;
+    uint32_t listed;  // entries used in bad_list
+    // first bad waves: wave, xcc, se, sh, cu, simd, mask of failed phases
+    uint32_t bad_list[NA_VALU_MAX_LISTED][7];
+} na_valu_sweep_result;
+
+static const char* const vs_phase_names[VS_PHASES + 2] = {
+    "rf", "rf_inv", "i32", "f32", "f64", "pk", "xlane", "trans", "stream", "index", "placement"};
+
+// Source slot of destination slot i under cross-lane move n of the xlane
+// phase. Single-operand moves have 64 slots (the lanes); the two swaps have
+// 128: A's lanes, then B's.
+static int vs_xlane_source(int n, int i) {
+    const int l = i & 63;
+    switch (n) {
+        case 0: return (l & ~3) | ((l + 1) & 3);
+        case 1: return (l & ~15) | ((l - 3) & 15);
+        case 2: return l ^ 15;
+        case 3: return l ^ 7;
+        case 4: return (5 * l + 3) & 63;
+        case 5:
+        case 6: {
+            const int half = n == 5 ? 16 : 32;
+            if (i < 64) return l & half ? 64 + l - half : l;  // A': B's row below, or A
+            return l & half ? i : l + half;                   // B': B, or A's row above
+        }
+        default: return VS_BCAST_LANE;
+    }
+}
+static int vs_xlane_slots(int n) { return n == 5 || n == 6 ? 128 : 64; }
+
+// Pure host code: the source table of move n (see vs_xlane_source).
+extern "C" int na_valu_sweep_xlane_table(int move, int* out, int n) {
+    if (move < 0 || move >= VS_XLANE_MOVES || out == nullptr || n < vs_xlane_slots(move)) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_valu_sweep_xlane_table: need move in 0..%d (got %d) and room for its "
+                      "slots (out %p, n %d)",
+                      VS_XLANE_MOVES - 1, move, (void*)out, n);
+        return NA_ERR_ARG;
+    }
+    for (int i = 0; i < vs_xlane_slots(move); ++i) out[i] = vs_xlane_source(move, i);
+    return vs_xlane_slots(move);
+}
+
+static inline uint64_t vs_hfold(uint64_t c, uint64_t v) { return c * MS_G + v; }
+static inline uint64_t vs_hfold_int(uint64_t c, int v) { return c * MS_G + (uint64_t)(int64_t)v; }
+
+// x = fma(x, a, b) chains on exact small integers, in integer arithmetic:
+// `n` chains from h(p, first + j), x kept to `mask` + 1 values around 0.
+static void vs_chain_init(uint64_t base, int p, uint64_t first, int n, int mask, int* x, int* a,
+                          int* b) {
+    for (int j = 0; j < n; ++j) {
+        const uint64_t e = vs_h(base, p, first + j);
+        x[j] = (int)(e & mask) - (mask + 1) / 2;
+        a[j] = (int)((e >> 12) % 7) - 3;
+        b[j] = (int)((e >> 20) % 15) - 7;
+    }
+}
+static inline int vs_chain_step(uint64_t& c, int x, int a, int b, int mask) {
+    const int r = x * a + b;
+    c = vs_hfold_int(c, r);
+    return (r & mask) - (mask + 1) / 2;
+}
+
+// The VS_PHASES checksums of wave `wave` (trans: 0).
+static void vs_expected(uint64_t base, uint64_t wave, int iters, uint64_t* out) {
+    for (int p = 0; p < VS_PHASES; ++p) out[p] = 0;
+    uint32_t xl[64];
+    uint64_t xc[64];
+    for (uint32_t l = 0; l < 64; ++l) {
+        const uint64_t gl = wave * 64 + l;
+        for (int p = VS_RF; p <= VS_RF_INV; ++p) {
+            const uint32_t pol = p == VS_RF ? 0u : ~0u;
+            uint32_t x = (uint32_t)(vs_h(base, p, gl) >> 32), lo = 0, hi = 0;
+            for (int s = 0; s < VS_SLOTS; ++s) {
+                x = x * VS_LCG_A + VS_LCG_B;
+                lo = lo * VS_FOLD_LO + (x ^ pol);
+                hi = hi * VS_FOLD_HI + (x ^ pol);
+            }
+            out[p] += ((uint64_t)hi << 32) | lo;
+        }
+        {
+            const uint64_t h0 = vs_h(base, VS_I32, 2 * gl), h1 = vs_h(base, VS_I32, 2 * gl + 1);
+            uint32_t a = (uint32_t)h0, b = (uint32_t)(h0 >> 32), c = (uint32_t)h1,
+                     d = (uint32_t)(h1 >> 32);
+            uint64_t sum = 0;
+            for (uint32_t k = 0; k < VS_STEPS; ++k) {
+                const uint32_t t = a * b;
+                const uint32_t u = (uint32_t)(((uint64_t)c * (d | 1u)) >> 32);
+                const uint64_t m = (uint64_t)a * c + (((uint64_t)d << 32) | b);
+                const uint32_t e = t + u + (uint32_t)m;
+                const uint32_t f = e ^ (uint32_t)(m >> 32) ^ k;
+                const uint32_t g = (uint32_t)((((uint64_t)f << 32) | e) >> (k & 31));
+                const uint64_t gt = ((uint64_t)g << 32) | t;
+                uint32_t q = 0;
+                for (int i = 0; i < 4; ++i)
+                    q |= (uint32_t)((gt >> (8 * ((VS_PERM_SEL >> (8 * i)) & 7))) & 0xFF) << (8 * i);
+                sum = vs_hfold(sum, ((uint64_t)q << 32) | g);
+                sum = vs_hfold(sum, ((uint64_t)f << 32) | e);
+                a = q + 0x9E3779B9u, b = g | 1u, c = f, d = e + k;
+            }
+            out[VS_I32] += sum;
+        }
+        for (int p = VS_F32; p <= VS_F64; ++p) {
+            int x[4], a[4], b[4];
+            vs_chain_init(base, p, 4 * gl, 4, 0xFFF, x, a, b);
+            uint64_t sum = 0;
+            for (int k = 0; k < VS_STEPS; ++k)
+                for (int j = 0; j < 4; ++j) x[j] = vs_chain_step(sum, x[j], a[j], b[j], 0xFFF);
+            out[p] += sum;
+        }
+        {
+            int x[8], a[8], b[8];
+            vs_chain_init(base, VS_PK, 8 * gl, 4, 0xFFF, x, a, b);
+            vs_chain_init(base, VS_PK, 8 * gl + 4, 4, 0x3FF, x + 4, a + 4, b + 4);
+            uint64_t sum = 0;
+            for (int k = 0; k < VS_STEPS; ++k)
+                for (int j = 0; j < 8; ++j)
+                    x[j] = vs_chain_step(sum, x[j], a[j], b[j], j < 4 ? 0xFFF : 0x3FF);
+            out[VS_PK] += sum;
+        }
+        {
+            uint64_t sum = 0;
+            for (int j = 0; j < 2 * VS_STREAM_PAIRS; ++j) {
+                const uint64_t e = vs_h(base, VS_STREAM, 2 * VS_STREAM_PAIRS * gl + j);
+                const int x = (int)(e & 0xFFF) - 2048, b = (int)((e >> 13) % 5) - 2;
+                const bool neg = (e >> 12) & 1;
+                sum = vs_hfold_int(sum, !neg ? x + iters * b : (iters & 1) ? b - x : x);
+            }
+            out[VS_STREAM] += sum;
+        }
+        xl[l] = (uint32_t)(vs_h(base, VS_XLANE, gl) >> 32);
+        xc[l] = 0;
+    }
+    // xlane: the whole wave at once
+    for (int n = 0; n < VS_XLANE_MOVES; ++n) {
+        uint32_t src[128], moved[128];
+        const uint32_t other = n == 5 ? 0xA5A5A5A5u : 0x5A5A5A5Au;
+        for (int l = 0; l < 64; ++l) src[l] = xl[l], src[64 + l] = xl[l] ^ other;
+        const int slots = vs_xlane_slots(n);
+        for (int i = 0; i < slots; ++i) moved[i] = src[vs_xlane_source(n, i)];
+        for (uint32_t l = 0; l < 64; ++l) {
+            uint32_t v = moved[l];
+            if (slots == 128) v ^= (moved[64 + l] << 7) | (moved[64 + l] >> 25);
+            xl[l] = v * VS_XLANE_MUL + l;
+            xc[l] = vs_hfold(xc[l], xl[l]);
+        }
+    }
+    for (int l = 0; l < 64; ++l) out[VS_XLANE] += xc[l];
+}
+
+// R of the register-file phases: a0..a255 and v32..v255.
+extern "C" int na_valu_sweep_slots() { return VS_SLOTS; }
+
+// Pure host code: the VS_PHASES checksums of one wave, in the order of the
+// VS_* codes; the trans entry, which has no host reference, is 0.
+extern "C" int na_valu_sweep_expected(unsigned long long seed, unsigned long long wave, int iters,
+                                      uint64_t* checksums) {
+    if (iters < 1 || iters > VS_MAX_ITERS || checksums == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_valu_sweep_expected: need iters in 1..%d, the bound to which the stream "
+                      "phase is exact (got %d), and room for %d checksums",
+                      VS_MAX_ITERS, iters, VS_PHASES);
+        return NA_ERR_ARG;
+    }
+    vs_expected(seed * MS_G, wave, iters, checksums);
+    return NA_OK;
+}
+
+// One launch of `workgroups` x 4 waves, HIP-event timed; out receives the
+// 4 * workgroups records. Argument errors are detected before any HIP call.
+extern "C" int na_valu_sweep_run(int dev, int workgroups, int iters, unsigned long long seed,
+                                 na_valu_record* out, long long n_out, double* ms) {
+    if (workgroups < 1 || workgroups > NA_VALU_MAX_WORKGROUPS || iters < 1 ||
+        iters > VS_MAX_ITERS || out == nullptr ||
+        n_out < (long long)workgroups * MS_WAVES_PER_WG) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_valu_sweep_run: need workgroups in 1..%d (got %d), iters in 1..%d, the "
+                      "bound to which the stream phase is exact (got %d), and room for 4 records "
+                      "per workgroup (out %p, n_out %lld)",
+                      NA_VALU_MAX_WORKGROUPS, workgroups, VS_MAX_ITERS, iters, (void*)out, n_out);
+        return NA_ERR_ARG;
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    // more than half of the CU's LDS, so one workgroup per CU (see ms_run)
+    size_t lds_bytes = prop.sharedMemPerBlock;
+    if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
+    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
+    dev_buf<na_valu_record> d;
+    HIP_CHECK(d.alloc(n));
+    // a record its wave never wrote carries no valid wave index and fails the verify
+    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(na_valu_record)));
+    dev_events<2> ev;
+    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(ev.e[0]));
+    valu_sweep_kernel<<<dim3((unsigned)workgroups), dim3(VS_BLOCK), lds_bytes>>>(
+        d.p, seed * MS_G, iters);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[1]));
+    HIP_CHECK(hipEventSynchronize(ev.e[1]));
+    float elapsed = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(na_valu_record), hipMemcpyDeviceToHost));
+    if (ms) *ms = (double)elapsed;
+    return NA_OK;
+}
+
+// Pure host code: record i is wave i. A wave is bad when an exact phase
+// checksum is not the expected one, when its in-kernel register-file count is
+// not zero, when its trans checksum is not the strict majority's (with fewer
+// than 3 records or no strict majority the phase is left unchecked, which is
+// no failure), when it does not carry its own index, or when its workgroup's
+// four waves are not on four distinct SIMDs of one CU. Returns NA_ERR_VERIFY
+// on any bad wave; *res is filled either way.
+extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int iters,
+                                    unsigned long long seed, na_valu_sweep_result* res) {
+    if (recs == nullptr || n < 1 || iters < 1 || iters > VS_MAX_ITERS || res == nullptr) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_valu_sweep_verify: need records, n >= 1 (got %lld), iters in 1..%d (got "
+                      "%d) and a result pointer",
+                      n, VS_MAX_ITERS, iters);
+        return NA_ERR_ARG;
+    }
+    std::memset(res, 0, sizeof(*res));
+    res->waves = (uint64_t)n;
+    res->rf_first_slot = res->rf_first_lane = ~0u;
+    const uint64_t base = seed * MS_G;
+
+    // trans: the strict majority by the Boyer-Moore vote, then a count
+    res->trans_unchecked = 1;
+    if (n >= 3) {
+        uint64_t cand = 0;
+        long long votes = 0, count = 0;
+        for (long long i = 0; i < n; ++i) {
+            if (votes == 0) cand = recs[i].checksum[VS_TRANS];
+            votes += recs[i].checksum[VS_TRANS] == cand ? 1 : -1;
+        }
+        for (long long i = 0; i < n; ++i) count += recs[i].checksum[VS_TRANS] == cand;
+        if (2 * count > n) {
+            res->trans_unchecked = 0;
+            res->trans_consensus = cand;
+        }
+    }
+
+    std::vector<uint32_t> mask((size_t)n, 0);
+    std::vector<bool> cu_seen(1 << 11, false), simd_seen(1 << 13, false);
+    std::vector<double> mhz, rate, cycles;
+    mhz.reserve((size_t)n), rate.reserve((size_t)n), cycles.reserve((size_t)n);
+    double min_rate = 0.0;
+    for (long long i = 0; i < n; ++i) {
+        const na_valu_record& r = recs[i];
+        const uint32_t key = ms_cu_key(r);
+        if (!cu_seen[key]) {
+            cu_seen[key] = true;
+            res->cus_seen++;
+        }
+        if (!simd_seen[key << 2 | (r.simd & 3)]) {
+            simd_seen[key << 2 | (r.simd & 3)] = true;
+            res->simds_seen++;
+        }
+        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
+        if (r.cycles) {
+            const double f = (double)iters * VS_FLOP_PER_ITER / (double)r.cycles;
+            if (rate.empty() || f < min_rate) min_rate = f;
+            rate.push_back(f);
+            cycles.push_back((double)r.cycles);
+        }
+        uint64_t want[VS_PHASES];
+        vs_expected(base, (uint64_t)i, iters, want);
+        for (int p = 0; p < VS_PHASES; ++p)
+            if (p != VS_TRANS && r.checksum[p] != want[p]) mask[i] |= 1u << p;
+        if (r.rf_bad != 0 && !(mask[i] & (1u << VS_RF | 1u << VS_RF_INV)))
+            mask[i] |= 1u << (r.rf_first_slot != ~0u && r.rf_first_slot >= 512 ? VS_RF_INV : VS_RF);
+        if (!res->trans_unchecked && r.checksum[VS_TRANS] != res->trans_consensus)
+            mask[i] |= 1u << VS_TRANS;
+        if (r.wave != (uint64_t)i) mask[i] |= NA_VALU_BAD_INDEX;
+    }
+    for (long long g = 0; g + MS_WAVES_PER_WG <= n; g += MS_WAVES_PER_WG) {
+        unsigned simds = 0;
+        bool one_cu = true;
+        for (int k = 0; k < MS_WAVES_PER_WG; ++k) {
+            simds |= 1u << (recs[g + k].simd & 3);
+            one_cu = one_cu && ms_cu_key(recs[g + k]) == ms_cu_key(recs[g]);
+        }
+        if (simds != 15u || !one_cu)
+            for (int k = 0; k < MS_WAVES_PER_WG; ++k) mask[g + k] |= NA_VALU_BAD_PLACEMENT;
+    }
+    for (long long i = 0; i < n; ++i) {
+        if (mask[i] == 0) continue;
+        const na_valu_record& r = recs[i];
+        if (res->bad_waves++ == 0 && (mask[i] & (1u << VS_RF | 1u << VS_RF_INV)) && r.rf_bad) {
+            res->rf_bad = r.rf_bad;
+            res->rf_first_slot = r.rf_first_slot;
+            res->rf_first_lane = r.rf_first_lane;
+            res->rf_xor = r.rf_xor;
+        }
+        if (res->listed < NA_VALU_MAX_LISTED) {
+            const uint32_t row[7] = {(uint32_t)i, r.xcc, r.se, r.sh, r.cu, r.simd, mask[i]};
+            std::memcpy(res->bad_list[res->listed++], row, sizeof(row));
+        }
+    }
+    res->clock_mhz = ls_median(mhz);
+    res->median_flop_per_clk = ls_median(rate);
+    res->min_flop_per_clk = min_rate;
+    res->median_cycles = (uint64_t)ls_median(cycles);
+    res->tflops = res->median_flop_per_clk * (double)res->simds_seen * res->clock_mhz / 1e6;
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->bad_list[0];
+    char phases[96] = "";
+    for (int p = 0, at = 0; p < VS_PHASES + 2; ++p)
+        if (u[6] >> p & 1)
+            at += std::snprintf(phases + at, sizeof(phases) - at, "%s%s", at ? "," : "",
+                                vs_phase_names[p]);
+    char where[128] = "";
+    if (res->rf_bad) {
+        const uint32_t slot = res->rf_first_slot & 511;
+        std::snprintf(where, sizeof(where),
+                      ", %u wrong registers, first %c%u lane %u, failing bits 0x%08x", res->rf_bad,
+                      slot < 256 ? 'a' : 'v', slot < 256 ? slot : slot - 256 + VS_FIRST_VGPR,
+                      res->rf_first_lane, res->rf_xor);
+    }
+    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                  "valu sweep: %llu of %llu waves wrong, first wave %u in phase %s on "
+                  "xcc%u.se%u.sh%u.cu%u.simd%u%s",
+                  (unsigned long long)res->bad_waves, (unsigned long long)res->waves, u[0], phases,
+                  u[1], u[2], u[3], u[4], u[5], where);
+    return NA_ERR_VERIFY;
+}
+
+// Whole sweep: one untimed warm-up launch, the timed launch, the verify.
+// workgroups 0 = 4 per CU, iters 0 = NA_VALU_DEFAULT_ITERS. res->tflops is
+// the chip-wide rate of the stream phase from the in-kernel stamps alone,
+// not the launch's event time (which includes the other phases): the median
+// SIMD's FLOP per shader clock, on every SIMD that took part, at the median
+// measured clock.
+extern "C" int na_valu_sweep(int dev, int workgroups, int iters, unsigned long long seed,
+                             na_valu_sweep_result* res) {
+    if (res == nullptr || workgroups < 0 || workgroups > NA_VALU_MAX_WORKGROUPS || iters < 0 ||
+        iters > VS_MAX_ITERS) {
+        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
+                      "na_valu_sweep: need workgroups in 0..%d (got %d), iters in 0..%d (got %d) "
+                      "and a result pointer",
+                      NA_VALU_MAX_WORKGROUPS, workgroups, VS_MAX_ITERS, iters);
+        return NA_ERR_ARG;
+    }
+    if (iters == 0) iters = NA_VALU_DEFAULT_ITERS;
+    if (workgroups == 0) {
+        hipDeviceProp_t prop;
+        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+        workgroups = 4 * prop.multiProcessorCount;
+    }
+    std::vector<na_valu_record> recs((size_t)workgroups * MS_WAVES_PER_WG);
+    double ms = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
+        int rc = na_valu_sweep_run(dev, workgroups, iters, seed, recs.data(),
+                                   (long long)recs.size(), &ms);
+        if (rc != NA_OK) return rc;
+    }
+    return na_valu_sweep_verify(recs.data(), (long long)recs.size(), iters, seed, res);
 }
