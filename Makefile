@@ -25,8 +25,7 @@ build: nodeagent jsontree objmodel revstore
 
 nodeagent: gpu_provisioner_amd/_native/libmi355x_nodeagent.so
 
-gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip nodeagent/memtest.h nodeagent/mfmasweep.h \
-    nodeagent/mfma_frag.h
+gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip $(wildcard nodeagent/*.h)
 	mkdir -p gpu_provisioner_amd/_native
 	$(HIPCC) --offload-arch=$(OFFLOAD_ARCH) -O3 -shared -fPIC $< -o $@
 

@@ -800,55 +800,92 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"HBM memtest: {res.describe()}")
 
-    # -- chip-wide matrix-core sweep ------------------------------------------
+    # -- what the chip-wide sweeps' wrappers share ------------------------------
+
+    def _sweep_run(self, what, record_type, n, *args) -> tuple:
+        """``na_<what>`` with ``args`` ahead of the ``n`` records it fills.
+        Returns ``(records, ms)``."""
+        recs = (record_type * max(n, 1))()
+        ms = ctypes.c_double(0)
+        dev = args[0]
+        rc = getattr(self.lib, f"na_{what}")(*args, recs, ctypes.c_longlong(n), ctypes.byref(ms))
+        if rc != NA_OK:
+            raise NodeAgentError(f"{what}({dev}): {self._err()}")
+        return recs, ms.value
+
+    def _sweep_verify(self, what, recs, args, res, wrap, empty) -> tuple:
+        """``na_<what>`` on ``recs`` with ``args`` between the record count and
+        the C result ``res``. Returns ``(rc, wrap(res))``, or ``(rc, empty())``
+        when the call itself was refused."""
+        rc = getattr(self.lib, f"na_{what}")(
+            recs, ctypes.c_longlong(len(recs)), *args, ctypes.byref(res)
+        )
+        return rc, wrap(res) if rc in (NA_OK, NA_ERR_VERIFY) else empty()
+
+    # The matrix-core sweep's two families, "mfma" (dtypes) and "mx" (formats),
+    # differ in symbol prefix, code table and the word for a code.
 
     @staticmethod
-    def _mfma_dtype(dtype: str) -> int:
-        if dtype not in MFMA_SWEEP_DTYPES:
-            raise NodeAgentError(f"mfma sweep: dtype {dtype!r} is not one of bf16, fp8")
-        return MFMA_SWEEP_DTYPES[dtype]
+    def _matrix_code(fam: str, name: str) -> int:
+        codes, word = ((MFMA_SWEEP_DTYPES, "dtype") if fam == "mfma"
+                       else (MX_SWEEP_FORMATS, "format"))
+        if name not in codes:
+            raise NodeAgentError(f"{fam} sweep: {word} {name!r} is not one of {', '.join(codes)}")
+        return codes[name]
+
+    def _matrix_sweep_expected(self, fam, wave, outer, seed) -> int:
+        out = ctypes.c_uint64(0)
+        rc = getattr(self.lib, f"na_{fam}_sweep_expected")(
+            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
+        )
+        if rc != NA_OK:
+            raise NodeAgentError(f"{fam}_sweep_expected: {self._err()}")
+        return out.value
+
+    def _matrix_sweep_run(self, fam, dev, name, workgroups, outer, seed) -> tuple:
+        return self._sweep_run(
+            f"{fam}_sweep_run", MfmaRecord, max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG,
+            dev, self._matrix_code(fam, name), workgroups, outer, ctypes.c_ulonglong(seed),
+        )
+
+    def _matrix_sweep_verify(self, fam, recs, outer, seed, name) -> tuple:
+        return self._sweep_verify(
+            f"{fam}_sweep_verify", recs, (outer, ctypes.c_ulonglong(seed)), _MfmaSweepResultC(),
+            lambda res: MfmaSweepResult._from_c(name, res), lambda: MfmaSweepResult(name),
+        )
+
+    def _matrix_sweep(self, fam, dev, name, workgroups, outer, seed) -> MfmaSweepResult:
+        res = _MfmaSweepResultC()
+        tflops = ctypes.c_double(0)
+        rc = getattr(self.lib, f"na_{fam}_sweep")(
+            dev, self._matrix_code(fam, name), workgroups, outer, ctypes.c_ulonglong(seed),
+            ctypes.byref(res), ctypes.byref(tflops),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            raise NodeAgentError(f"{fam}_sweep({dev}, {name}): {self._err()}")
+        return MfmaSweepResult._from_c(name, res, tflops.value)
+
+    # -- chip-wide matrix-core sweep ------------------------------------------
 
     def mfma_sweep_expected(self, wave: int, outer: int,
                             seed: int = DEFAULT_MFMA_SWEEP_SEED) -> int:
         """Checksum wave ``wave`` must report after ``outer`` folds (host
         arithmetic only; needs no GPU)."""
-        out = ctypes.c_uint64(0)
-        rc = self.lib.na_mfma_sweep_expected(
-            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
-        )
-        if rc != NA_OK:
-            raise NodeAgentError(f"mfma_sweep_expected: {self._err()}")
-        return out.value
+        return self._matrix_sweep_expected("mfma", wave, outer, seed)
 
     def mfma_sweep_run(self, dev: int, dtype: str = "bf16", workgroups: int = 1,
                        outer: int = 1, seed: int = DEFAULT_MFMA_SWEEP_SEED) -> tuple:
         """One launch of ``workgroups`` x 4 waves, each through ``outer``
         folds of 64 MFMAs. Returns ``(records, ms)``: a ctypes array of
         ``MfmaRecord`` (record i is wave i) and the HIP-event time."""
-        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
-        recs = (MfmaRecord * max(n, 1))()
-        ms = ctypes.c_double(0)
-        rc = self.lib.na_mfma_sweep_run(
-            dev, self._mfma_dtype(dtype), workgroups, outer, ctypes.c_ulonglong(seed),
-            recs, ctypes.c_longlong(n), ctypes.byref(ms),
-        )
-        if rc != NA_OK:
-            raise NodeAgentError(f"mfma_sweep_run({dev}): {self._err()}")
-        return recs, ms.value
+        return self._matrix_sweep_run("mfma", dev, dtype, workgroups, outer, seed)
 
     def mfma_sweep_verify(self, recs, outer: int, seed: int = DEFAULT_MFMA_SWEEP_SEED,
                           dtype: str = "bf16") -> tuple:
         """Compare every record against the host reference. Returns
         ``(rc, MfmaSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad wave,
         and ``na_last_error`` then names the first failing unit."""
-        res = _MfmaSweepResultC()
-        rc = self.lib.na_mfma_sweep_verify(
-            recs, ctypes.c_longlong(len(recs)), outer, ctypes.c_ulonglong(seed),
-            ctypes.byref(res),
-        )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            return rc, MfmaSweepResult(dtype)
-        return rc, MfmaSweepResult._from_c(dtype, res)
+        return self._matrix_sweep_verify("mfma", recs, outer, seed, dtype)
 
     def mfma_sweep(self, dev: int, dtype: str = "bf16", workgroups: int = 0, outer: int = 0,
                    seed: int = DEFAULT_MFMA_SWEEP_SEED) -> MfmaSweepResult:
@@ -859,15 +896,7 @@ class NodeAgent:
         back in the result (``.ok`` False) with the units they ran on, not
         as an exception. The TFLOP/s figure is on small-integer operands held
         in registers and is not comparable to GEMM benchmarks."""
-        res = _MfmaSweepResultC()
-        tflops = ctypes.c_double(0)
-        rc = self.lib.na_mfma_sweep(
-            dev, self._mfma_dtype(dtype), workgroups, outer, ctypes.c_ulonglong(seed),
-            ctypes.byref(res), ctypes.byref(tflops),
-        )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            raise NodeAgentError(f"mfma_sweep({dev}, {dtype}): {self._err()}")
-        return MfmaSweepResult._from_c(dtype, res, tflops.value)
+        return self._matrix_sweep("mfma", dev, dtype, workgroups, outer, seed)
 
     def _run_mfma_sweep(self, g: GPUReport) -> None:
         for dtype in ("bf16", "fp8"):
@@ -889,49 +918,21 @@ class NodeAgent:
 
     # -- chip-wide MX sweep ------------------------------------------------------
 
-    @staticmethod
-    def _mx_format(fmt: str) -> int:
-        if fmt not in MX_SWEEP_FORMATS:
-            raise NodeAgentError(f"mx sweep: format {fmt!r} is not one of fp4, fp6")
-        return MX_SWEEP_FORMATS[fmt]
-
     def mx_sweep_expected(self, wave: int, outer: int, seed: int = DEFAULT_MX_SWEEP_SEED) -> int:
         """Checksum wave ``wave`` of the MX sweep must report after ``outer``
         folds, in either format (host arithmetic only; needs no GPU)."""
-        out = ctypes.c_uint64(0)
-        rc = self.lib.na_mx_sweep_expected(
-            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
-        )
-        if rc != NA_OK:
-            raise NodeAgentError(f"mx_sweep_expected: {self._err()}")
-        return out.value
+        return self._matrix_sweep_expected("mx", wave, outer, seed)
 
     def mx_sweep_run(self, dev: int, fmt: str = "fp4", workgroups: int = 1, outer: int = 1,
                      seed: int = DEFAULT_MX_SWEEP_SEED) -> tuple:
         """As ``mfma_sweep_run``, on v_mfma_scale_f32_16x16x128_f8f6f4 with
         operands in ``fmt`` ("fp4" = E2M1, "fp6" = E2M3) and scales of 1.0."""
-        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
-        recs = (MfmaRecord * max(n, 1))()
-        ms = ctypes.c_double(0)
-        rc = self.lib.na_mx_sweep_run(
-            dev, self._mx_format(fmt), workgroups, outer, ctypes.c_ulonglong(seed),
-            recs, ctypes.c_longlong(n), ctypes.byref(ms),
-        )
-        if rc != NA_OK:
-            raise NodeAgentError(f"mx_sweep_run({dev}): {self._err()}")
-        return recs, ms.value
+        return self._matrix_sweep_run("mx", dev, fmt, workgroups, outer, seed)
 
     def mx_sweep_verify(self, recs, outer: int, seed: int = DEFAULT_MX_SWEEP_SEED,
                         fmt: str = "fp4") -> tuple:
         """As ``mfma_sweep_verify``, against the MX sweep's reference."""
-        res = _MfmaSweepResultC()
-        rc = self.lib.na_mx_sweep_verify(
-            recs, ctypes.c_longlong(len(recs)), outer, ctypes.c_ulonglong(seed),
-            ctypes.byref(res),
-        )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            return rc, MfmaSweepResult(fmt)
-        return rc, MfmaSweepResult._from_c(fmt, res)
+        return self._matrix_sweep_verify("mx", recs, outer, seed, fmt)
 
     def mx_sweep(self, dev: int, fmt: str = "fp4", workgroups: int = 0, outer: int = 0,
                  seed: int = DEFAULT_MX_SWEEP_SEED) -> MfmaSweepResult:
@@ -939,15 +940,7 @@ class NodeAgent:
         ``fmt``: every SIMD of every CU issues fp4 / fp6 MFMAs, each wave
         checked bit-exactly. 65536 FLOP per MFMA; the TFLOP/s caveat of
         ``mfma_sweep`` applies."""
-        res = _MfmaSweepResultC()
-        tflops = ctypes.c_double(0)
-        rc = self.lib.na_mx_sweep(
-            dev, self._mx_format(fmt), workgroups, outer, ctypes.c_ulonglong(seed),
-            ctypes.byref(res), ctypes.byref(tflops),
-        )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            raise NodeAgentError(f"mx_sweep({dev}, {fmt}): {self._err()}")
-        return MfmaSweepResult._from_c(fmt, res, tflops.value)
+        return self._matrix_sweep("mx", dev, fmt, workgroups, outer, seed)
 
     def _run_mx_sweep(self, g: GPUReport) -> None:
         for fmt in MX_SWEEP_FORMATS:
@@ -994,16 +987,10 @@ class NodeAgent:
         on the leading ``lds_bytes`` of its LDS (0 = all of it) with ``iters``
         stream passes. Returns ``(records, ms)``: a ctypes array of
         ``LdsRecord`` (record i is workgroup i) and the HIP-event time."""
-        n = max(workgroups, 0)
-        recs = (LdsRecord * max(n, 1))()
-        ms = ctypes.c_double(0)
-        rc = self.lib.na_lds_sweep_run(
+        return self._sweep_run(
+            "lds_sweep_run", LdsRecord, max(workgroups, 0),
             dev, workgroups, ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed),
-            recs, ctypes.c_longlong(n), ctypes.byref(ms),
         )
-        if rc != NA_OK:
-            raise NodeAgentError(f"lds_sweep_run({dev}): {self._err()}")
-        return recs, ms.value
 
     def lds_sweep_verify(self, recs, lds_bytes: int, iters: int,
                          seed: int = DEFAULT_LDS_SWEEP_SEED) -> tuple:
@@ -1011,14 +998,11 @@ class NodeAgent:
         explicit, as for ``lds_sweep_expected``). Returns ``(rc,
         LdsSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad workgroup, and
         ``na_last_error`` then names the first failing phase and CU."""
-        res = _LdsSweepResultC()
-        rc = self.lib.na_lds_sweep_verify(
-            recs, ctypes.c_longlong(len(recs)), ctypes.c_longlong(lds_bytes), iters,
-            ctypes.c_ulonglong(seed), ctypes.byref(res),
+        return self._sweep_verify(
+            "lds_sweep_verify", recs,
+            (ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed)),
+            _LdsSweepResultC(), LdsSweepResult._from_c, LdsSweepResult,
         )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            return rc, LdsSweepResult()
-        return rc, LdsSweepResult._from_c(res)
 
     def lds_sweep(self, dev: int, workgroups: int = 0, lds_bytes: int = 0, iters: int = 0,
                   seed: int = DEFAULT_LDS_SWEEP_SEED) -> LdsSweepResult:
@@ -1088,29 +1072,20 @@ class NodeAgent:
         """One launch of ``workgroups`` x 4 waves, each through every phase
         with ``iters`` stream rounds. Returns ``(records, ms)``: a ctypes
         array of ``ValuRecord`` (record i is wave i) and the HIP-event time."""
-        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
-        recs = (ValuRecord * max(n, 1))()
-        ms = ctypes.c_double(0)
-        rc = self.lib.na_valu_sweep_run(
-            dev, workgroups, iters, ctypes.c_ulonglong(seed), recs, ctypes.c_longlong(n),
-            ctypes.byref(ms),
+        return self._sweep_run(
+            "valu_sweep_run", ValuRecord, max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG,
+            dev, workgroups, iters, ctypes.c_ulonglong(seed),
         )
-        if rc != NA_OK:
-            raise NodeAgentError(f"valu_sweep_run({dev}): {self._err()}")
-        return recs, ms.value
 
     def valu_sweep_verify(self, recs, iters: int, seed: int = DEFAULT_VALU_SWEEP_SEED) -> tuple:
         """Compare every record against the host reference and, for the
         transcendental phase, against the other records. Returns ``(rc,
         ValuSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad wave, and
         ``na_last_error`` then names the first failing unit and phase."""
-        res = _ValuSweepResultC()
-        rc = self.lib.na_valu_sweep_verify(
-            recs, ctypes.c_longlong(len(recs)), iters, ctypes.c_ulonglong(seed), ctypes.byref(res)
+        return self._sweep_verify(
+            "valu_sweep_verify", recs, (iters, ctypes.c_ulonglong(seed)),
+            _ValuSweepResultC(), ValuSweepResult._from_c, ValuSweepResult,
         )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            return rc, ValuSweepResult()
-        return rc, ValuSweepResult._from_c(res)
 
     def valu_sweep(self, dev: int, workgroups: int = 0, iters: int = 0,
                    seed: int = DEFAULT_VALU_SWEEP_SEED) -> ValuSweepResult:

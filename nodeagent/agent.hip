@@ -15,7 +15,10 @@
 // instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h), an
 // opt-in chip-wide LDS sweep (every LDS access path on every CU, ldssweep.h),
 // an opt-in chip-wide vector-unit sweep (register file and VALU of every
-// SIMD, valusweep.h), and the xGMI peer-to-peer link matrix.
+// SIMD, valusweep.h), and the xGMI peer-to-peer link matrix. The three
+// chip-wide sweeps share their device-side stamp and placement record
+// (sweep_common.h) and their host side ("Shared host side of the chip-wide
+// sweeps" below): a further sweep starts from those.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
 // consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
@@ -25,6 +28,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -52,6 +56,15 @@
 static char na_last_error_buf[512];
 
 extern "C" const char* na_last_error() { return na_last_error_buf; }
+
+// Every argument error: the message into na_last_error, NA_ERR_ARG back.
+__attribute__((format(printf, 1, 2))) static int arg_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(na_last_error_buf, sizeof(na_last_error_buf), fmt, ap);
+    va_end(ap);
+    return NA_ERR_ARG;
+}
 
 // ---------------------------------------------------------------------------
 // HIP resources: HIP_CHECK returns from the middle of a function, so whatever
@@ -400,10 +413,9 @@ static const mfma_check* mfma_check_args(const char* fn, int kind, const void* w
     if (kind >= 0 && kind < NA_MFMA_KINDS && words != nullptr &&
         n_words >= mfma_checks[kind].words())
         return &mfma_checks[kind];
-    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the "
-                  "32x32 tile (words %p, n_words %d)",
-                  fn, NA_MFMA_KINDS - 1, kind, words, n_words);
+    arg_error("%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the 32x32 "
+              "tile (words %p, n_words %d)",
+              fn, NA_MFMA_KINDS - 1, kind, words, n_words);
     return nullptr;
 }
 
@@ -479,13 +491,10 @@ extern "C" int na_mfma_mx_tile_check(int dev) {
 // Pure host code, for tests of the encodings and the packing.
 extern "C" int na_mx_decode(int fmt, int code, float* value) {
     if (fmt < 0 || fmt >= MX_FORMATS || code < 0 || code >= 1 << mx_bits(fmt) ||
-        value == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_mx_decode: need fmt in 0..%d (got %d), a code of its width (got %d) "
-                      "and a result pointer",
-                      MX_FORMATS - 1, fmt, code);
-        return NA_ERR_ARG;
-    }
+        value == nullptr)
+        return arg_error("na_mx_decode: need fmt in 0..%d (got %d), a code of its width (got %d) "
+                         "and a result pointer",
+                         MX_FORMATS - 1, fmt, code);
     *value = mx_decode(fmt, (unsigned)code);
     return NA_OK;
 }
@@ -496,14 +505,11 @@ extern "C" int na_mx_pack(int fmt, const int* codes, int n, uint32_t* words, int
     bool ok = fmt >= 0 && fmt < MX_FORMATS && codes != nullptr && words != nullptr && n > 0 &&
               n % 32 == 0 && (long long)n_words * 32 >= (long long)n * mx_bits(fmt);
     for (int i = 0; ok && i < n; ++i) ok = codes[i] >= 0 && codes[i] < 1 << mx_bits(fmt);
-    if (!ok) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_mx_pack: need fmt in 0..%d (got %d), n a positive multiple of 32 (got "
-                      "%d) of codes of that width, and room for n * width / 32 words (codes %p, "
-                      "words %p, n_words %d)",
-                      MX_FORMATS - 1, fmt, n, (const void*)codes, (void*)words, n_words);
-        return NA_ERR_ARG;
-    }
+    if (!ok)
+        return arg_error("na_mx_pack: need fmt in 0..%d (got %d), n a positive multiple of 32 "
+                         "(got %d) of codes of that width, and room for n * width / 32 words "
+                         "(codes %p, words %p, n_words %d)",
+                         MX_FORMATS - 1, fmt, n, (const void*)codes, (void*)words, n_words);
     const int regs = mx_bits(fmt);  // 32 elements of `width` bits fill `width` registers
     std::memset(words, 0, (size_t)(n / 32) * regs * sizeof(uint32_t));
     for (int i = 0; i < n; ++i) {
@@ -563,10 +569,9 @@ static float mx_check_want(const mx_check& c, int i, int j) {
 static const mx_check* mx_check_args(const char* fn, int kind, const void* words, int n_words) {
     if (kind >= 0 && kind < NA_MX_KINDS && words != nullptr && n_words >= mx_checks[kind].words())
         return &mx_checks[kind];
-    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the "
-                  "32x32 tile (words %p, n_words %d)",
-                  fn, NA_MX_KINDS - 1, kind, words, n_words);
+    arg_error("%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the 32x32 "
+              "tile (words %p, n_words %d)",
+              fn, NA_MX_KINDS - 1, kind, words, n_words);
     return nullptr;
 }
 
@@ -782,13 +787,10 @@ struct mt_dev_accum {
 };
 
 static int mt_check_args(const char* fn, const void* dptr, long long bytes) {
-    if (dptr == nullptr || ((uintptr_t)dptr & 15) != 0 || bytes <= 0 || (bytes & 15) != 0) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "%s: pointer %p must be 16-byte aligned and bytes (%lld) a positive "
-                      "multiple of 16",
-                      fn, dptr, bytes);
-        return NA_ERR_ARG;
-    }
+    if (dptr == nullptr || ((uintptr_t)dptr & 15) != 0 || bytes <= 0 || (bytes & 15) != 0)
+        return arg_error("%s: pointer %p must be 16-byte aligned and bytes (%lld) a positive "
+                         "multiple of 16",
+                         fn, dptr, bytes);
     return NA_OK;
 }
 
@@ -822,11 +824,7 @@ extern "C" int na_memtest_verify(int dev, void* dptr, long long bytes, unsigned 
                                  int invert, int flip, na_memtest_result* out) {
     int rc = mt_check_args("na_memtest_verify", dptr, bytes);
     if (rc != NA_OK) return rc;
-    if (out == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_memtest_verify: out must not be null");
-        return NA_ERR_ARG;
-    }
+    if (out == nullptr) return arg_error("na_memtest_verify: out must not be null");
     HIP_CHECK(hipSetDevice(dev));
     mt_dev_accum acc;
     rc = acc.init();
@@ -849,13 +847,10 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
                                      unsigned long long seed, na_memtest_result* out,
                                      double* gbs, double* pass_gbs) {
     bytes &= ~15LL;
-    if (bytes < 16 || rounds < 1 || out == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_hbm_memtest: need bytes >= 16 (got %lld), rounds >= 1 (got %d) and a "
-                      "result pointer",
-                      bytes, rounds);
-        return NA_ERR_ARG;
-    }
+    if (bytes < 16 || rounds < 1 || out == nullptr)
+        return arg_error("na_hbm_memtest: need bytes >= 16 (got %lld), rounds >= 1 (got %d) and a "
+                         "result pointer",
+                         bytes, rounds);
     HIP_CHECK(hipSetDevice(dev));
     const size_t nvec = (size_t)bytes / 16;
     std::vector<dev_buf<mt_vec>> chunks;
@@ -924,6 +919,126 @@ extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned lon
                               na_memtest_result* out, double* gbs) {
     return na_hbm_memtest_passes(dev, bytes, rounds, seed, out, gbs, nullptr);
 }
+
+// ---------------------------------------------------------------------------
+// Shared host side of the chip-wide sweeps (device side: sweep_common.h)
+// ---------------------------------------------------------------------------
+//
+// Each sweep below (matrix cores, LDS, vector unit) is a kernel that leaves
+// one record per wave or workgroup, a *_run that launches it once, a pure-host
+// *_verify that recomputes every record's checksums, and an entry point that
+// runs twice and verifies. A sweep owns its reference, its verdict rules, its
+// messages and its argument checks; the launch (sweep_launch), the defaults
+// and the warm-up (sweep_defaults, sweep_twice) and the bookkeeping over the
+// records (sweep_census, median_of) are here, for the next sweep too.
+
+#include "sweep_common.h"
+
+#define SWEEP_MAX_LISTED 8
+
+// The dynamic LDS the sweep kernels are launched with: the device's whole
+// per-workgroup allocation, as na_lds_selftest launches with. It is more
+// than half of the CU's LDS, so one workgroup per CU.
+static int sweep_lds_bytes(int dev, size_t* bytes) {
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    *bytes = std::min<size_t>(prop.sharedMemPerBlock, MS_CU_LDS_BYTES);
+    return NA_OK;
+}
+
+// What 0 means to the whole-sweep entry points: four workgroups per CU, and
+// the sweep's default count of folds, passes or rounds.
+static int sweep_defaults(int dev, int* workgroups, int* iters, int default_iters) {
+    if (*iters == 0) *iters = default_iters;
+    if (*workgroups == 0) {
+        hipDeviceProp_t prop;
+        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+        *workgroups = 4 * prop.multiProcessorCount;
+    }
+    return NA_OK;
+}
+
+// One HIP-event timed launch on `dev`: launch(records) starts the kernel on n
+// device records, which come back in out. A record its wave or workgroup
+// never wrote stays 0xFF, carries no valid index and fails the verify.
+template <typename R, typename LAUNCH>
+static int sweep_launch(int dev, size_t n, R* out, double* ms, LAUNCH launch) {
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<R> d;
+    HIP_CHECK(d.alloc(n));
+    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(R)));
+    dev_events<2> ev;
+    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(ev.e[0]));
+    launch(d.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[1]));
+    HIP_CHECK(hipEventSynchronize(ev.e[1]));
+    float elapsed = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(R), hipMemcpyDeviceToHost));
+    if (ms) *ms = (double)elapsed;
+    return NA_OK;
+}
+
+// run() twice: the first is the untimed warm-up, the second leaves its
+// records and its time.
+template <typename RUN>
+static int sweep_twice(RUN run) {
+    int rc = run();
+    return rc != NA_OK ? rc : run();
+}
+
+// 0 for none.
+static double median_of(std::vector<double>& v) {
+    if (v.empty()) return 0.0;
+    std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
+    return v[v.size() / 2];
+}
+
+// Who took part and who failed, over any of the sweeps' records. A unit is
+// (xcc, se, sh, cu, simd), simd 0 for the records that are per CU.
+struct sweep_census {
+    std::vector<bool> cu_seen, simd_seen, cu_bad;
+    std::vector<double> mhz;  // cycles / realtime x 100 MHz, per record
+    uint64_t cus_seen = 0, simds_seen = 0, bad_cus = 0;
+    uint32_t first_bad[5] = {}, listed = 0;  // the first bad unit; 0s for none
+    uint32_t bad_list[SWEEP_MAX_LISTED][5] = {};  // the first distinct bad units
+
+    sweep_census() : cu_seen(1 << 11), simd_seen(1 << 13), cu_bad(1 << 11) {}
+
+    template <typename R>
+    void see(const R& r, uint32_t simd = 0) {
+        const uint32_t key = ms_cu_key(r), simd_key = key << 2 | (simd & 3);
+        if (!cu_seen[key]) cu_seen[key] = true, cus_seen++;
+        if (!simd_seen[simd_key]) simd_seen[simd_key] = true, simds_seen++;
+        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
+    }
+
+    template <typename R>
+    void mark_bad(const R& r, uint32_t simd = 0) {
+        const uint32_t key = ms_cu_key(r), unit[5] = {r.xcc, r.se, r.sh, r.cu, simd};
+        if (!cu_bad[key]) cu_bad[key] = true, bad_cus++;
+        if (listed == 0) std::memcpy(first_bad, unit, sizeof(unit));
+        bool known = false;
+        for (uint32_t k = 0; k < listed && !known; ++k)
+            known = std::memcmp(bad_list[k], unit, sizeof(unit)) == 0;
+        if (!known && listed < SWEEP_MAX_LISTED)
+            std::memcpy(bad_list[listed++], unit, sizeof(unit));
+    }
+
+    // The leading W fields of the first bad unit and of the listed ones, into
+    // a result struct's arrays.
+    template <int W>
+    void bad_units(uint32_t (&first)[W], uint32_t (&list)[SWEEP_MAX_LISTED][W],
+                   uint32_t* n) const {
+        *n = listed;
+        std::memcpy(first, first_bad, sizeof(first));
+        for (uint32_t k = 0; k < listed; ++k) std::memcpy(list[k], bad_list[k], sizeof(first));
+    }
+
+    double clock_mhz() { return median_of(mhz); }
+};
 
 // ---------------------------------------------------------------------------
 // Chip-wide matrix-core sweep (kernel in mfmasweep.h)
@@ -1019,12 +1134,9 @@ static const ms_family ms_mx = {"na_mx_sweep", "mx sweep", "format 0 (fp4) or 1 
 // wave checksum to S(outer) * sum_l P_l.
 static int ms_expected(const ms_family& fam, unsigned long long seed, unsigned long long wave,
                        int outer, uint64_t* checksum) {
-    if (outer < 1 || checksum == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "%s_expected: need outer >= 1 (got %d) and a result pointer", fam.prefix,
-                      outer);
-        return NA_ERR_ARG;
-    }
+    if (outer < 1 || checksum == nullptr)
+        return arg_error("%s_expected: need outer >= 1 (got %d) and a result pointer", fam.prefix,
+                         outer);
     const uint64_t g2 = MS_G * MS_G;
     *checksum = ms_geometric_sum(g2 * g2, (uint64_t)outer) *
                 ms_wave_p_sum(seed * MS_G, wave, fam.k_len);
@@ -1037,50 +1149,22 @@ static int ms_run(const ms_family& fam, int dev, int code, int workgroups, int o
                   unsigned long long seed, na_mfma_record* out, long long n_out, double* ms) {
     if ((code != 0 && code != 1) || workgroups < 1 || workgroups > NA_MFMA_MAX_WORKGROUPS ||
         outer < 1 || outer > NA_MFMA_MAX_OUTER || out == nullptr ||
-        n_out < (long long)workgroups * MS_WAVES_PER_WG) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "%s_run: need %s (got %d), workgroups in "
-                      "1..%d (got %d), outer in 1..%d (got %d) and room for 4 records per "
-                      "workgroup (out %p, n_out %lld)",
-                      fam.prefix, fam.codes, code, NA_MFMA_MAX_WORKGROUPS, workgroups,
-                      NA_MFMA_MAX_OUTER, outer, (void*)out, n_out);
-        return NA_ERR_ARG;
-    }
-    HIP_CHECK(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    // the whole per-workgroup allocation, as na_lds_selftest launches with:
-    // more than half of the CU's LDS, so one workgroup per CU
-    size_t lds_bytes = prop.sharedMemPerBlock;
-    if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
-    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
-    dev_buf<na_mfma_record> d;
-    HIP_CHECK(d.alloc(n));
-    // a record its wave never wrote carries no valid wave index and fails the verify
-    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(na_mfma_record)));
-    dev_events<2> ev;
-    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
-    const mt_u64 base = seed * MS_G;
-    dim3 grid((unsigned)workgroups), block(MS_BLOCK);
-    HIP_CHECK(hipEventRecord(ev.e[0]));
+        n_out < (long long)workgroups * MS_WAVES_PER_WG)
+        return arg_error("%s_run: need %s (got %d), workgroups in 1..%d (got %d), outer in 1..%d "
+                         "(got %d) and room for 4 records per workgroup (out %p, n_out %lld)",
+                         fam.prefix, fam.codes, code, NA_MFMA_MAX_WORKGROUPS, workgroups,
+                         NA_MFMA_MAX_OUTER, outer, (void*)out, n_out);
+    size_t lds_bytes = 0;
+    int rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
     static void (*const kernels[MS_DTYPES])(na_mfma_record*, mt_u64, int) = {
         mfma_sweep_kernel<MS_BF16>, mfma_sweep_kernel<MS_FP8>, mfma_sweep_kernel<MS_FP4>,
         mfma_sweep_kernel<MS_FP6>};
-    kernels[fam.first + code]<<<grid, block, lds_bytes>>>(d.p, base, outer);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[1]));
-    HIP_CHECK(hipEventSynchronize(ev.e[1]));
-    float elapsed = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
-    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(na_mfma_record), hipMemcpyDeviceToHost));
-    if (ms) *ms = (double)elapsed;
-    return NA_OK;
-}
-
-// any of the sweeps' record types
-template <typename R>
-static inline uint32_t ms_cu_key(const R& r) {
-    return ((r.xcc & 15) << 7) | ((r.se & 3) << 5) | ((r.sh & 1) << 4) | (r.cu & 15);
+    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
+    return sweep_launch(dev, n, out, ms, [&](na_mfma_record* records) {
+        kernels[fam.first + code]<<<dim3((unsigned)workgroups), dim3(MS_BLOCK), lds_bytes>>>(
+            records, seed * MS_G, outer);
+    });
 }
 
 // Pure host code: record i is wave i. A wave is bad when its checksum is
@@ -1088,51 +1172,29 @@ static inline uint32_t ms_cu_key(const R& r) {
 // NA_ERR_VERIFY on any bad wave; *res is filled either way.
 static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long n, int outer,
                      unsigned long long seed, na_mfma_sweep_result* res) {
-    if (recs == nullptr || n < 1 || outer < 1 || res == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "%s_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) "
-                      "and a result pointer",
-                      fam.prefix, n, outer);
-        return NA_ERR_ARG;
-    }
+    if (recs == nullptr || n < 1 || outer < 1 || res == nullptr)
+        return arg_error("%s_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) and a "
+                         "result pointer",
+                         fam.prefix, n, outer);
     std::memset(res, 0, sizeof(*res));
     res->waves = (uint64_t)n;
     res->first_bad_wave = UINT64_MAX;
     const uint64_t base = seed * MS_G, g2 = MS_G * MS_G;
     const uint64_t s = ms_geometric_sum(g2 * g2, (uint64_t)outer);
-    std::vector<bool> seen(1 << 11, false), bad(1 << 11, false);
-    std::vector<double> mhz;
-    mhz.reserve((size_t)n);
+    sweep_census census;
     for (long long i = 0; i < n; ++i) {
         const na_mfma_record& r = recs[i];
-        const uint32_t key = ms_cu_key(r);
-        if (!seen[key]) {
-            seen[key] = true;
-            res->units_seen++;
-        }
-        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
+        census.see(r, r.simd);
         if (r.checksum == s * ms_wave_p_sum(base, (uint64_t)i, fam.k_len) && r.wave == (uint64_t)i)
             continue;
         res->bad_waves++;
-        if (!bad[key]) {
-            bad[key] = true;
-            res->bad_units++;
-        }
-        const uint32_t unit[5] = {r.xcc, r.se, r.sh, r.cu, r.simd};
-        if (res->first_bad_wave == UINT64_MAX) {
-            res->first_bad_wave = (uint64_t)i;
-            std::memcpy(res->first_bad_unit, unit, sizeof(unit));
-        }
-        bool listed = false;
-        for (uint32_t k = 0; k < res->listed && !listed; ++k)
-            listed = std::memcmp(res->bad_list[k], unit, sizeof(unit)) == 0;
-        if (!listed && res->listed < NA_MFMA_MAX_LISTED)
-            std::memcpy(res->bad_list[res->listed++], unit, sizeof(unit));
+        if (res->first_bad_wave == UINT64_MAX) res->first_bad_wave = (uint64_t)i;
+        census.mark_bad(r, r.simd);
     }
-    if (!mhz.empty()) {
-        std::nth_element(mhz.begin(), mhz.begin() + mhz.size() / 2, mhz.end());
-        res->clock_mhz = mhz[mhz.size() / 2];
-    }
+    res->units_seen = census.cus_seen;
+    res->bad_units = census.bad_cus;
+    res->clock_mhz = census.clock_mhz();
+    census.bad_units(res->first_bad_unit, res->bad_list, &res->listed);
     if (res->bad_waves == 0) return NA_OK;
     const uint32_t* u = res->first_bad_unit;
     std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
@@ -1150,26 +1212,19 @@ static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long
 // fold over the event time.
 static int ms_sweep(const ms_family& fam, int dev, int code, int workgroups, int outer,
                     unsigned long long seed, na_mfma_sweep_result* res, double* tflops) {
-    if (res == nullptr || workgroups < 0 || workgroups > NA_MFMA_MAX_WORKGROUPS || outer < 0) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "%s: need workgroups in 0..%d (got %d), outer >= 0 (got %d) and "
-                      "a result pointer",
-                      fam.prefix, NA_MFMA_MAX_WORKGROUPS, workgroups, outer);
-        return NA_ERR_ARG;
-    }
-    if (outer == 0) outer = NA_MFMA_DEFAULT_OUTER;
-    if (workgroups == 0) {
-        hipDeviceProp_t prop;
-        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        workgroups = 4 * prop.multiProcessorCount;
-    }
+    if (res == nullptr || workgroups < 0 || workgroups > NA_MFMA_MAX_WORKGROUPS || outer < 0)
+        return arg_error("%s: need workgroups in 0..%d (got %d), outer >= 0 (got %d) and a result "
+                         "pointer",
+                         fam.prefix, NA_MFMA_MAX_WORKGROUPS, workgroups, outer);
+    int rc = sweep_defaults(dev, &workgroups, &outer, NA_MFMA_DEFAULT_OUTER);
+    if (rc != NA_OK) return rc;
     std::vector<na_mfma_record> recs((size_t)workgroups * MS_WAVES_PER_WG);
     double ms = 0.0;
-    for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
-        int rc = ms_run(fam, dev, code, workgroups, outer, seed, recs.data(),
-                        (long long)recs.size(), &ms);
-        if (rc != NA_OK) return rc;
-    }
+    rc = sweep_twice([&] {
+        return ms_run(fam, dev, code, workgroups, outer, seed, recs.data(),
+                      (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
     if (tflops)
         *tflops = (double)recs.size() * outer * MS_MFMA_PER_FOLD * MS_FLOP_PER_MFMA_K * fam.k_len /
                   (ms * 1e9);
@@ -1371,17 +1426,11 @@ static bool ls_bytes_ok(long long lds_bytes) {
 // lds_bytes 0, tests: sharedMemPerBlock, capped at 160 KiB and rounded down
 // to the sweep's granule.
 extern "C" int na_lds_sweep_allocation(int dev, long long* bytes) {
-    if (bytes == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_lds_sweep_allocation: need a result pointer");
-        return NA_ERR_ARG;
-    }
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    size_t alloc = prop.sharedMemPerBlock;
-    if (alloc > LS_MAX_BYTES) alloc = LS_MAX_BYTES;
-    *bytes = (long long)(alloc / LS_GRANULE * LS_GRANULE);
-    return NA_OK;
+    if (bytes == nullptr) return arg_error("na_lds_sweep_allocation: need a result pointer");
+    size_t alloc = 0;
+    int rc = sweep_lds_bytes(dev, &alloc);
+    if (rc == NA_OK) *bytes = (long long)(alloc / LS_GRANULE * LS_GRANULE);
+    return rc;
 }
 
 // Pure host code: the LS_PHASES checksums of one workgroup, in the order of
@@ -1389,13 +1438,10 @@ extern "C" int na_lds_sweep_allocation(int dev, long long* bytes) {
 // 4096..160 KiB); n is the room in `checksums`.
 extern "C" int na_lds_sweep_expected(unsigned long long seed, unsigned long long workgroup,
                                      long long lds_bytes, int iters, uint64_t* checksums, int n) {
-    if (!ls_bytes_ok(lds_bytes) || iters < 1 || checksums == nullptr || n < LS_PHASES) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_lds_sweep_expected: need lds_bytes a multiple of %d in %d..%d (got "
-                      "%lld), iters >= 1 (got %d) and room for %d checksums (n %d)",
-                      LS_GRANULE, LS_GRANULE, LS_MAX_BYTES, lds_bytes, iters, LS_PHASES, n);
-        return NA_ERR_ARG;
-    }
+    if (!ls_bytes_ok(lds_bytes) || iters < 1 || checksums == nullptr || n < LS_PHASES)
+        return arg_error("na_lds_sweep_expected: need lds_bytes a multiple of %d in %d..%d (got "
+                         "%lld), iters >= 1 (got %d) and room for %d checksums (n %d)",
+                         LS_GRANULE, LS_GRANULE, LS_MAX_BYTES, lds_bytes, iters, LS_PHASES, n);
     ls_sums(seed * MS_G, (uint32_t)lds_bytes).expected(workgroup, iters, checksums);
     return NA_OK;
 }
@@ -1408,27 +1454,21 @@ extern "C" int na_lds_sweep_run(int dev, int workgroups, long long lds_bytes, in
                                 double* ms) {
     if (workgroups < 1 || workgroups > NA_LDS_MAX_WORKGROUPS ||
         (lds_bytes != 0 && !ls_bytes_ok(lds_bytes)) || iters < 1 || iters > NA_LDS_MAX_ITERS ||
-        out == nullptr || n_out < (long long)workgroups) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_lds_sweep_run: need workgroups in 1..%d (got %d), lds_bytes 0 or a "
-                      "multiple of %d up to %d (got %lld), iters in 1..%d (got %d) and room for "
-                      "a record per workgroup (out %p, n_out %lld)",
-                      NA_LDS_MAX_WORKGROUPS, workgroups, LS_GRANULE, LS_MAX_BYTES, lds_bytes,
-                      NA_LDS_MAX_ITERS, iters, (void*)out, n_out);
-        return NA_ERR_ARG;
-    }
-    HIP_CHECK(hipSetDevice(dev));
+        out == nullptr || n_out < (long long)workgroups)
+        return arg_error("na_lds_sweep_run: need workgroups in 1..%d (got %d), lds_bytes 0 or a "
+                         "multiple of %d up to %d (got %lld), iters in 1..%d (got %d) and room "
+                         "for a record per workgroup (out %p, n_out %lld)",
+                         NA_LDS_MAX_WORKGROUPS, workgroups, LS_GRANULE, LS_MAX_BYTES, lds_bytes,
+                         NA_LDS_MAX_ITERS, iters, (void*)out, n_out);
+    HIP_CHECK(hipSetDevice(dev));  // for the upload below, ahead of sweep_launch
     long long alloc = 0;
     int rc = na_lds_sweep_allocation(dev, &alloc);
     if (rc != NA_OK) return rc;
     if (lds_bytes == 0) lds_bytes = alloc;
-    if (lds_bytes > alloc || alloc < LS_GRANULE) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_lds_sweep_run: lds_bytes %lld exceeds the device's %lld-byte "
-                      "per-workgroup LDS allocation",
-                      lds_bytes, alloc);
-        return NA_ERR_ARG;
-    }
+    if (lds_bytes > alloc || alloc < LS_GRANULE)
+        return arg_error("na_lds_sweep_run: lds_bytes %lld exceeds the device's %lld-byte "
+                         "per-workgroup LDS allocation",
+                         lds_bytes, alloc);
     // the dma phases' source: pattern LS_PAT_DMA
     const uint32_t W = (uint32_t)lds_bytes / 4;
     const mt_u64 base = seed * MS_G;
@@ -1438,31 +1478,11 @@ extern "C" int na_lds_sweep_run(int dev, int workgroups, long long lds_bytes, in
     HIP_CHECK(src.alloc(pattern.size()));
     HIP_CHECK(hipMemcpy(src.p, pattern.data(), pattern.size() * sizeof(uint32_t),
                         hipMemcpyHostToDevice));
-    const size_t n = (size_t)workgroups;
-    dev_buf<na_lds_record> d;
-    HIP_CHECK(d.alloc(n));
-    // a record its workgroup never wrote carries no valid index and fails the verify
-    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(na_lds_record)));
-    dev_events<2> ev;
-    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(ev.e[0]));
-    // the whole allocation whatever lds_bytes is: one workgroup per CU
-    lds_sweep_kernel<<<dim3((unsigned)workgroups), dim3(LS_BLOCK), (size_t)alloc>>>(
-        d.p, src.p, base, (uint32_t)lds_bytes, iters);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[1]));
-    HIP_CHECK(hipEventSynchronize(ev.e[1]));
-    float elapsed = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
-    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(na_lds_record), hipMemcpyDeviceToHost));
-    if (ms) *ms = (double)elapsed;
-    return NA_OK;
-}
-
-static double ls_median(std::vector<double>& v) {
-    if (v.empty()) return 0.0;
-    std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
-    return v[v.size() / 2];
+    return sweep_launch(dev, (size_t)workgroups, out, ms, [&](na_lds_record* records) {
+        // the whole allocation whatever lds_bytes is: one workgroup per CU
+        lds_sweep_kernel<<<dim3((unsigned)workgroups), dim3(LS_BLOCK), (size_t)alloc>>>(
+            records, src.p, base, (uint32_t)lds_bytes, iters);
+    });
 }
 
 // Pure host code: record i is workgroup i. A workgroup is bad when a phase
@@ -1471,14 +1491,11 @@ static double ls_median(std::vector<double>& v) {
 // any bad workgroup; *res is filled either way.
 extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long long lds_bytes,
                                    int iters, unsigned long long seed, na_lds_sweep_result* res) {
-    if (recs == nullptr || n < 1 || !ls_bytes_ok(lds_bytes) || iters < 1 || res == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_lds_sweep_verify: need records, n >= 1 (got %lld), lds_bytes a "
-                      "multiple of %d in %d..%d (got %lld), iters >= 1 (got %d) and a result "
-                      "pointer",
-                      n, LS_GRANULE, LS_GRANULE, LS_MAX_BYTES, lds_bytes, iters);
-        return NA_ERR_ARG;
-    }
+    if (recs == nullptr || n < 1 || !ls_bytes_ok(lds_bytes) || iters < 1 || res == nullptr)
+        return arg_error("na_lds_sweep_verify: need records, n >= 1 (got %lld), lds_bytes a "
+                         "multiple of %d in %d..%d (got %lld), iters >= 1 (got %d) and a result "
+                         "pointer",
+                         n, LS_GRANULE, LS_GRANULE, LS_MAX_BYTES, lds_bytes, iters);
     std::memset(res, 0, sizeof(*res));
     res->workgroups = (uint64_t)n;
     res->first_bad_workgroup = res->first_bad_offset = UINT64_MAX;
@@ -1487,24 +1504,12 @@ extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long 
     // every C-th workgroup shares a rotation, hence its checksums
     std::vector<uint64_t> want((size_t)sums.C * LS_PHASES);
     for (uint32_t r = 0; r < sums.C; ++r) sums.expected(r, iters, &want[(size_t)r * LS_PHASES]);
-    std::vector<bool> seen(1 << 11, false), bad(1 << 11, false);
-    std::vector<double> mhz, rate;
-    mhz.reserve((size_t)n), rate.reserve((size_t)n);
-    double min_rate = 0.0, max_rate = 0.0;
+    sweep_census census;
+    std::vector<double> rate;
     for (long long i = 0; i < n; ++i) {
         const na_lds_record& r = recs[i];
-        const uint32_t key = ms_cu_key(r);
-        if (!seen[key]) {
-            seen[key] = true;
-            res->units_seen++;
-        }
-        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
-        if (r.cycles) {
-            const double b = (double)iters * (double)lds_bytes / (double)r.cycles;
-            if (rate.empty() || b < min_rate) min_rate = b;
-            if (b > max_rate) max_rate = b;
-            rate.push_back(b);
-        }
+        census.see(r);
+        if (r.cycles) rate.push_back((double)iters * (double)lds_bytes / (double)r.cycles);
         const uint64_t* w = &want[(size_t)(i % sums.C) * LS_PHASES];
         uint32_t phase = 0;
         while (phase < LS_PHASES && r.checksum[phase] == w[phase]) ++phase;
@@ -1513,31 +1518,26 @@ extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long 
         if (phase == LS_PHASES && r.workgroup == (uint64_t)i) continue;
         // `phase` failed; LS_PHASES: the record is only in the wrong place
         res->bad_workgroups++;
-        if (!bad[key]) {
-            bad[key] = true;
-            res->bad_units++;
-        }
-        const uint32_t unit[4] = {r.xcc, r.se, r.sh, r.cu};
+        census.mark_bad(r);
         if (res->first_bad_workgroup == UINT64_MAX) {
             res->first_bad_workgroup = (uint64_t)i;
             res->first_bad_phase = phase;
-            std::memcpy(res->first_bad_unit, unit, sizeof(unit));
             if (r.bad_words != 0 && r.bad_phase == phase) {
                 res->bad_words = r.bad_words;
                 res->first_bad_offset = r.first_bad_offset;
                 res->xor_mask = r.xor_mask;
             }
         }
-        bool listed = false;
-        for (uint32_t k = 0; k < res->listed && !listed; ++k)
-            listed = std::memcmp(res->bad_list[k], unit, sizeof(unit)) == 0;
-        if (!listed && res->listed < NA_LDS_MAX_LISTED)
-            std::memcpy(res->bad_list[res->listed++], unit, sizeof(unit));
     }
-    res->clock_mhz = ls_median(mhz);
-    res->median_bytes_per_clk = ls_median(rate);
-    res->min_bytes_per_clk = min_rate;
-    res->max_bytes_per_clk = max_rate;
+    res->units_seen = census.cus_seen;
+    res->bad_units = census.bad_cus;
+    res->clock_mhz = census.clock_mhz();
+    census.bad_units(res->first_bad_unit, res->bad_list, &res->listed);
+    if (!rate.empty()) {
+        res->min_bytes_per_clk = *std::min_element(rate.begin(), rate.end());
+        res->max_bytes_per_clk = *std::max_element(rate.begin(), rate.end());
+    }
+    res->median_bytes_per_clk = median_of(rate);
     if (res->bad_workgroups == 0) return NA_OK;
     const uint32_t* u = res->first_bad_unit;
     char where[128] = "";
@@ -1571,33 +1571,22 @@ extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long 
 extern "C" int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int iters,
                             unsigned long long seed, na_lds_sweep_result* res, double* gbs) {
     if (res == nullptr || workgroups < 0 || workgroups > NA_LDS_MAX_WORKGROUPS ||
-        (lds_bytes != 0 && !ls_bytes_ok(lds_bytes)) || iters < 0 || iters > NA_LDS_MAX_ITERS) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_lds_sweep: need workgroups in 0..%d (got %d), lds_bytes 0 or a "
-                      "multiple of %d up to %d (got %lld), iters in 0..%d (got %d) and a result "
-                      "pointer",
-                      NA_LDS_MAX_WORKGROUPS, workgroups, LS_GRANULE, LS_MAX_BYTES, lds_bytes,
-                      NA_LDS_MAX_ITERS, iters);
-        return NA_ERR_ARG;
-    }
-    if (iters == 0) iters = NA_LDS_DEFAULT_ITERS;
-    if (workgroups == 0) {
-        hipDeviceProp_t prop;
-        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        workgroups = 4 * prop.multiProcessorCount;
-    }
-    if (lds_bytes == 0) {
-        int rc = na_lds_sweep_allocation(dev, &lds_bytes);
-        if (rc != NA_OK) return rc;
-    }
+        (lds_bytes != 0 && !ls_bytes_ok(lds_bytes)) || iters < 0 || iters > NA_LDS_MAX_ITERS)
+        return arg_error("na_lds_sweep: need workgroups in 0..%d (got %d), lds_bytes 0 or a "
+                         "multiple of %d up to %d (got %lld), iters in 0..%d (got %d) and a "
+                         "result pointer",
+                         NA_LDS_MAX_WORKGROUPS, workgroups, LS_GRANULE, LS_MAX_BYTES, lds_bytes,
+                         NA_LDS_MAX_ITERS, iters);
+    int rc = sweep_defaults(dev, &workgroups, &iters, NA_LDS_DEFAULT_ITERS);
+    if (rc == NA_OK && lds_bytes == 0) rc = na_lds_sweep_allocation(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
     std::vector<na_lds_record> recs((size_t)workgroups);
-    double ms = 0.0;
-    for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
-        int rc = na_lds_sweep_run(dev, workgroups, lds_bytes, iters, seed, recs.data(),
-                                  (long long)recs.size(), &ms);
-        if (rc != NA_OK) return rc;
-    }
-    int rc = na_lds_sweep_verify(recs.data(), (long long)recs.size(), lds_bytes, iters, seed, res);
+    rc = sweep_twice([&] {
+        return na_lds_sweep_run(dev, workgroups, lds_bytes, iters, seed, recs.data(),
+                                (long long)recs.size(), nullptr);
+    });
+    if (rc != NA_OK) return rc;
+    rc = na_lds_sweep_verify(recs.data(), (long long)recs.size(), lds_bytes, iters, seed, res);
     if (gbs && (rc == NA_OK || rc == NA_ERR_VERIFY))
         *gbs = res->median_bytes_per_clk * (double)res->units_seen * res->clock_mhz / 1000.0;
     return rc;
@@ -1675,13 +1664,10 @@ static int vs_xlane_slots(int n) { return n == 5 || n == 6 ? 128 : 64; }
 
 // Pure host code: the source table of move n (see vs_xlane_source).
 extern "C" int na_valu_sweep_xlane_table(int move, int* out, int n) {
-    if (move < 0 || move >= VS_XLANE_MOVES || out == nullptr || n < vs_xlane_slots(move)) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_valu_sweep_xlane_table: need move in 0..%d (got %d) and room for its "
-                      "slots (out %p, n %d)",
-                      VS_XLANE_MOVES - 1, move, (void*)out, n);
-        return NA_ERR_ARG;
-    }
+    if (move < 0 || move >= VS_XLANE_MOVES || out == nullptr || n < vs_xlane_slots(move))
+        return arg_error("na_valu_sweep_xlane_table: need move in 0..%d (got %d) and room for its "
+                         "slots (out %p, n %d)",
+                         VS_XLANE_MOVES - 1, move, (void*)out, n);
     for (int i = 0; i < vs_xlane_slots(move); ++i) out[i] = vs_xlane_source(move, i);
     return vs_xlane_slots(move);
 }
@@ -1800,13 +1786,10 @@ extern "C" int na_valu_sweep_slots() { return VS_SLOTS; }
 // VS_* codes; the trans entry, which has no host reference, is 0.
 extern "C" int na_valu_sweep_expected(unsigned long long seed, unsigned long long wave, int iters,
                                       uint64_t* checksums) {
-    if (iters < 1 || iters > VS_MAX_ITERS || checksums == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_valu_sweep_expected: need iters in 1..%d, the bound to which the stream "
-                      "phase is exact (got %d), and room for %d checksums",
-                      VS_MAX_ITERS, iters, VS_PHASES);
-        return NA_ERR_ARG;
-    }
+    if (iters < 1 || iters > VS_MAX_ITERS || checksums == nullptr)
+        return arg_error("na_valu_sweep_expected: need iters in 1..%d, the bound to which the "
+                         "stream phase is exact (got %d), and room for %d checksums",
+                         VS_MAX_ITERS, iters, VS_PHASES);
     vs_expected(seed * MS_G, wave, iters, checksums);
     return NA_OK;
 }
@@ -1817,38 +1800,20 @@ extern "C" int na_valu_sweep_run(int dev, int workgroups, int iters, unsigned lo
                                  na_valu_record* out, long long n_out, double* ms) {
     if (workgroups < 1 || workgroups > NA_VALU_MAX_WORKGROUPS || iters < 1 ||
         iters > VS_MAX_ITERS || out == nullptr ||
-        n_out < (long long)workgroups * MS_WAVES_PER_WG) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_valu_sweep_run: need workgroups in 1..%d (got %d), iters in 1..%d, the "
-                      "bound to which the stream phase is exact (got %d), and room for 4 records "
-                      "per workgroup (out %p, n_out %lld)",
-                      NA_VALU_MAX_WORKGROUPS, workgroups, VS_MAX_ITERS, iters, (void*)out, n_out);
-        return NA_ERR_ARG;
-    }
-    HIP_CHECK(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    // more than half of the CU's LDS, so one workgroup per CU (see ms_run)
-    size_t lds_bytes = prop.sharedMemPerBlock;
-    if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
+        n_out < (long long)workgroups * MS_WAVES_PER_WG)
+        return arg_error("na_valu_sweep_run: need workgroups in 1..%d (got %d), iters in 1..%d, "
+                         "the bound to which the stream phase is exact (got %d), and room for 4 "
+                         "records per workgroup (out %p, n_out %lld)",
+                         NA_VALU_MAX_WORKGROUPS, workgroups, VS_MAX_ITERS, iters, (void*)out,
+                         n_out);
+    size_t lds_bytes = 0;
+    int rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
     const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
-    dev_buf<na_valu_record> d;
-    HIP_CHECK(d.alloc(n));
-    // a record its wave never wrote carries no valid wave index and fails the verify
-    HIP_CHECK(hipMemset(d.p, 0xFF, n * sizeof(na_valu_record)));
-    dev_events<2> ev;
-    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(ev.e[0]));
-    valu_sweep_kernel<<<dim3((unsigned)workgroups), dim3(VS_BLOCK), lds_bytes>>>(
-        d.p, seed * MS_G, iters);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev.e[1]));
-    HIP_CHECK(hipEventSynchronize(ev.e[1]));
-    float elapsed = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&elapsed, ev.e[0], ev.e[1]));
-    HIP_CHECK(hipMemcpy(out, d.p, n * sizeof(na_valu_record), hipMemcpyDeviceToHost));
-    if (ms) *ms = (double)elapsed;
-    return NA_OK;
+    return sweep_launch(dev, n, out, ms, [&](na_valu_record* records) {
+        valu_sweep_kernel<<<dim3((unsigned)workgroups), dim3(VS_BLOCK), lds_bytes>>>(
+            records, seed * MS_G, iters);
+    });
 }
 
 // Pure host code: record i is wave i. A wave is bad when an exact phase
@@ -1860,13 +1825,10 @@ extern "C" int na_valu_sweep_run(int dev, int workgroups, int iters, unsigned lo
 // on any bad wave; *res is filled either way.
 extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int iters,
                                     unsigned long long seed, na_valu_sweep_result* res) {
-    if (recs == nullptr || n < 1 || iters < 1 || iters > VS_MAX_ITERS || res == nullptr) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_valu_sweep_verify: need records, n >= 1 (got %lld), iters in 1..%d (got "
-                      "%d) and a result pointer",
-                      n, VS_MAX_ITERS, iters);
-        return NA_ERR_ARG;
-    }
+    if (recs == nullptr || n < 1 || iters < 1 || iters > VS_MAX_ITERS || res == nullptr)
+        return arg_error("na_valu_sweep_verify: need records, n >= 1 (got %lld), iters in 1..%d "
+                         "(got %d) and a result pointer",
+                         n, VS_MAX_ITERS, iters);
     std::memset(res, 0, sizeof(*res));
     res->waves = (uint64_t)n;
     res->rf_first_slot = res->rf_first_lane = ~0u;
@@ -1889,26 +1851,13 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
     }
 
     std::vector<uint32_t> mask((size_t)n, 0);
-    std::vector<bool> cu_seen(1 << 11, false), simd_seen(1 << 13, false);
-    std::vector<double> mhz, rate, cycles;
-    mhz.reserve((size_t)n), rate.reserve((size_t)n), cycles.reserve((size_t)n);
-    double min_rate = 0.0;
+    sweep_census census;
+    std::vector<double> rate, cycles;
     for (long long i = 0; i < n; ++i) {
         const na_valu_record& r = recs[i];
-        const uint32_t key = ms_cu_key(r);
-        if (!cu_seen[key]) {
-            cu_seen[key] = true;
-            res->cus_seen++;
-        }
-        if (!simd_seen[key << 2 | (r.simd & 3)]) {
-            simd_seen[key << 2 | (r.simd & 3)] = true;
-            res->simds_seen++;
-        }
-        if (r.realtime) mhz.push_back((double)r.cycles / (double)r.realtime * 100.0);
+        census.see(r, r.simd);
         if (r.cycles) {
-            const double f = (double)iters * VS_FLOP_PER_ITER / (double)r.cycles;
-            if (rate.empty() || f < min_rate) min_rate = f;
-            rate.push_back(f);
+            rate.push_back((double)iters * VS_FLOP_PER_ITER / (double)r.cycles);
             cycles.push_back((double)r.cycles);
         }
         uint64_t want[VS_PHASES];
@@ -1945,10 +1894,12 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
             std::memcpy(res->bad_list[res->listed++], row, sizeof(row));
         }
     }
-    res->clock_mhz = ls_median(mhz);
-    res->median_flop_per_clk = ls_median(rate);
-    res->min_flop_per_clk = min_rate;
-    res->median_cycles = (uint64_t)ls_median(cycles);
+    res->cus_seen = census.cus_seen;
+    res->simds_seen = census.simds_seen;
+    res->clock_mhz = census.clock_mhz();
+    if (!rate.empty()) res->min_flop_per_clk = *std::min_element(rate.begin(), rate.end());
+    res->median_flop_per_clk = median_of(rate);
+    res->median_cycles = (uint64_t)median_of(cycles);
     res->tflops = res->median_flop_per_clk * (double)res->simds_seen * res->clock_mhz / 1e6;
     if (res->bad_waves == 0) return NA_OK;
     const uint32_t* u = res->bad_list[0];
@@ -1982,25 +1933,17 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
 extern "C" int na_valu_sweep(int dev, int workgroups, int iters, unsigned long long seed,
                              na_valu_sweep_result* res) {
     if (res == nullptr || workgroups < 0 || workgroups > NA_VALU_MAX_WORKGROUPS || iters < 0 ||
-        iters > VS_MAX_ITERS) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "na_valu_sweep: need workgroups in 0..%d (got %d), iters in 0..%d (got %d) "
-                      "and a result pointer",
-                      NA_VALU_MAX_WORKGROUPS, workgroups, VS_MAX_ITERS, iters);
-        return NA_ERR_ARG;
-    }
-    if (iters == 0) iters = NA_VALU_DEFAULT_ITERS;
-    if (workgroups == 0) {
-        hipDeviceProp_t prop;
-        HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        workgroups = 4 * prop.multiProcessorCount;
-    }
+        iters > VS_MAX_ITERS)
+        return arg_error("na_valu_sweep: need workgroups in 0..%d (got %d), iters in 0..%d (got "
+                         "%d) and a result pointer",
+                         NA_VALU_MAX_WORKGROUPS, workgroups, VS_MAX_ITERS, iters);
+    int rc = sweep_defaults(dev, &workgroups, &iters, NA_VALU_DEFAULT_ITERS);
+    if (rc != NA_OK) return rc;
     std::vector<na_valu_record> recs((size_t)workgroups * MS_WAVES_PER_WG);
-    double ms = 0.0;
-    for (int pass = 0; pass < 2; ++pass) {  // pass 0 is the warm-up
-        int rc = na_valu_sweep_run(dev, workgroups, iters, seed, recs.data(),
-                                   (long long)recs.size(), &ms);
-        if (rc != NA_OK) return rc;
-    }
+    rc = sweep_twice([&] {
+        return na_valu_sweep_run(dev, workgroups, iters, seed, recs.data(),
+                                 (long long)recs.size(), nullptr);
+    });
+    if (rc != NA_OK) return rc;
     return na_valu_sweep_verify(recs.data(), (long long)recs.size(), iters, seed, res);
 }

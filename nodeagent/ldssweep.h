@@ -91,12 +91,12 @@
 #include <cstdint>
 
 #include "memtest.h"
-#include "mfmasweep.h"
+#include "sweep_common.h"
 
-#define LS_BLOCK 256         // four waves, as mfmasweep.h
+#define LS_BLOCK MS_BLOCK    // four waves, as every sweep
 #define LS_CHUNK_WORDS 256   // 1 KiB: the unit of rotation
 #define LS_GRANULE 4096      // lds_bytes is a multiple of this: one 16-byte access per thread
-#define LS_MAX_BYTES (160 * 1024)
+#define LS_MAX_BYTES MS_CU_LDS_BYTES
 #define LS_PERM(t) (((t) + 67u) & 255u)
 
 enum { LS_B32, LS_B128, LS_DMA16, LS_DMA4, LS_DMA12, LS_TR16, LS_ATOMIC, LS_STREAM, LS_PHASES };
@@ -241,8 +241,7 @@ lds_sweep_kernel(na_lds_record* __restrict__ records, const uint32_t* __restrict
                  mt_u64 base, uint32_t lds_bytes, int iters) {
 #if defined(__gfx950__)
     extern __shared__ __attribute__((aligned(16))) unsigned char ls_mem[];
-    const unsigned hw_id = __builtin_amdgcn_s_getreg(MS_GETREG(32, 0, 4));
-    const unsigned xcc_id = __builtin_amdgcn_s_getreg(MS_GETREG(4, 0, 20));
+    const ms_hw_where at = ms_where();
     const unsigned char* src = reinterpret_cast<const unsigned char*>(src_);
     ls_ctx x;
     x.mem = ls_mem;
@@ -331,10 +330,7 @@ lds_sweep_kernel(na_lds_record* __restrict__ records, const uint32_t* __restrict
     // from them.
     ls_fill128(x, LS_PAT_STREAM, rotw, 0);
     __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-    const mt_u64 t0 = __builtin_amdgcn_s_memtime();
-    const mt_u64 rt0 = __builtin_amdgcn_s_memrealtime();
-    __builtin_amdgcn_sched_barrier(0);
+    const ms_clock t0 = ms_stamp();
     {
         const mt_vec* v = reinterpret_cast<const mt_vec*>(ls_mem) + t;
         const uint32_t steps = C / 4;  // 4 KiB each: one vector per thread
@@ -383,10 +379,7 @@ lds_sweep_kernel(na_lds_record* __restrict__ records, const uint32_t* __restrict
         c[LS_STREAM] = s;
     }
     __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-    const mt_u64 t1 = __builtin_amdgcn_s_memtime();
-    const mt_u64 rt1 = __builtin_amdgcn_s_memrealtime();
-    __builtin_amdgcn_sched_barrier(0);
+    const ms_clock t1 = ms_stamp();
 
     // reduce: lanes by shuffle, the four waves through LDS
     for (int o = 32; o > 0; o >>= 1) {
@@ -422,13 +415,8 @@ lds_sweep_kernel(na_lds_record* __restrict__ records, const uint32_t* __restrict
         rec.first_bad_offset = bad ? (key & 0xFFFFFFFFULL) : ~0ULL;
         rec.bad_phase = bad ? (uint32_t)(key >> 32) : ~0u;
         rec.xor_mask = xm;
-        rec.cycles = t1 - t0;
-        rec.realtime = rt1 - rt0;
         rec.workgroup = blockIdx.x;
-        rec.xcc = xcc_id & 15;
-        rec.se = (hw_id >> 13) & 3;
-        rec.sh = (hw_id >> 12) & 1;
-        rec.cu = (hw_id >> 8) & 15;
+        ms_record_cu(rec, t0, t1, at);
         records[blockIdx.x] = rec;
     }
 #else

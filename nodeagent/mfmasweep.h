@@ -44,22 +44,16 @@
 
 #include "memtest.h"
 #include "mfma_frag.h"
+#include "sweep_common.h"
 
-#define MS_BLOCK 256  // four waves: one per SIMD of the CU
-#define MS_WAVES_PER_WG (MS_BLOCK / 64)
 #define MS_FRAGS 8
 #define MS_MFMA_PER_FOLD (MS_FRAGS * MS_FRAGS)
 #define MS_FLOP_PER_MFMA_K 512.0  // 16 x 16 x 2, per unit of K
 #define MS_MAX_K 128
-#define MS_G 0x9E3779B97F4A7C15ULL
 
 // MS_BF16 and MS_FP8 are the dtype codes of na_mfma_sweep*; the MX sweep's
 // format f (0 = fp4, 1 = fp6) is MS_FP4 + f.
 enum { MS_BF16 = 0, MS_FP8 = 1, MS_FP4 = 2, MS_FP6 = 3, MS_DTYPES };
-
-// s_getreg operand: SIZE-1 in 15:11, OFFSET in 10:6, register id in 5:0
-// (encodings: amd_device_functions.h). HW_ID is register 4, XCC_ID 20.
-#define MS_GETREG(size, offset, reg) ((((size)-1) << 11) | ((offset) << 6) | (reg))
 
 // One per wave, written by one lane. cycles/realtime are the deltas of
 // s_memtime (shader clock) and s_memrealtime (100 MHz) around the fold loop.
@@ -145,8 +139,7 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
     // the condition for back-to-back 16-cycle issue of this MFMA shape.
     typedef ms_traits<DTYPE> T;
     typedef typename T::frag frag;
-    const unsigned hw_id = __builtin_amdgcn_s_getreg(MS_GETREG(32, 0, 4));
-    const unsigned xcc_id = __builtin_amdgcn_s_getreg(MS_GETREG(4, 0, 20));
+    const ms_hw_where at = ms_where();
     const int l = threadIdx.x & 63;
     const mt_u64 w = (mt_u64)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6);
 
@@ -155,10 +148,7 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
 
     // The stamps bracket the whole loop, go only into the record, and no
     // output is computed from them.
-    __builtin_amdgcn_sched_barrier(0);
-    const mt_u64 t0 = __builtin_amdgcn_s_memtime();
-    const mt_u64 rt0 = __builtin_amdgcn_s_memrealtime();
-    __builtin_amdgcn_sched_barrier(0);
+    const ms_clock t0 = ms_stamp();
 
     // Software-pipelined by one fold: the checksum update of fold j-1 does
     // not depend on fold j's MFMAs, so its VALU work issues in their shadow.
@@ -171,23 +161,14 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
     }
     c = ms_update(c, d);
 
-    __builtin_amdgcn_sched_barrier(0);
-    const mt_u64 t1 = __builtin_amdgcn_s_memtime();
-    const mt_u64 rt1 = __builtin_amdgcn_s_memrealtime();
-    __builtin_amdgcn_sched_barrier(0);
+    const ms_clock t1 = ms_stamp();
 
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     if (l == 0) {
         na_mfma_record rec;
         rec.checksum = c;
-        rec.cycles = t1 - t0;
-        rec.realtime = rt1 - rt0;
         rec.wave = (uint32_t)w;
-        rec.xcc = xcc_id & 15;
-        rec.se = (hw_id >> 13) & 3;
-        rec.sh = (hw_id >> 12) & 1;
-        rec.cu = (hw_id >> 8) & 15;
-        rec.simd = (hw_id >> 4) & 3;
+        ms_record_simd(rec, t0, t1, at);
         records[w] = rec;
     }
 #else

@@ -116,7 +116,7 @@
 #include <cstdint>
 
 #include "memtest.h"
-#include "mfmasweep.h"
+#include "sweep_common.h"
 
 #define VS_BLOCK MS_BLOCK  // four waves: one per SIMD of the CU
 #define VS_FIRST_VGPR 32
@@ -419,8 +419,7 @@ __device__ inline mt_u64 vs_trans_phase(uint32_t l) {
 __global__ void __launch_bounds__(VS_BLOCK)
 valu_sweep_kernel(na_valu_record* __restrict__ records, mt_u64 base, int iters) {
 #if defined(__gfx950__)
-    const unsigned hw_id = __builtin_amdgcn_s_getreg(MS_GETREG(32, 0, 4));
-    const unsigned xcc_id = __builtin_amdgcn_s_getreg(MS_GETREG(4, 0, 20));
+    const ms_hw_where at = ms_where();
     const uint32_t l = threadIdx.x & 63;
     const mt_u64 w = (mt_u64)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6);
     const mt_u64 gl = w * 64 + l;
@@ -461,10 +460,7 @@ valu_sweep_kernel(na_valu_record* __restrict__ records, mt_u64 base, int iters) 
     }
     // The stamps bracket the whole loop, go only into the record, and no
     // output is computed from them.
-    __builtin_amdgcn_sched_barrier(0);
-    const mt_u64 t0 = __builtin_amdgcn_s_memtime();
-    const mt_u64 rt0 = __builtin_amdgcn_s_memrealtime();
-    __builtin_amdgcn_sched_barrier(0);
+    const ms_clock t0 = ms_stamp();
     // Four rounds per trip, then the remainder: the loop's scalar
     // instructions take issue slots of the one wave a SIMD has. The empty asm
     // keeps the rounds from being folded (see ms_fold).
@@ -481,10 +477,7 @@ valu_sweep_kernel(na_valu_record* __restrict__ records, mt_u64 base, int iters) 
         VS_ROUND
     }
 #undef VS_ROUND
-    __builtin_amdgcn_sched_barrier(0);
-    const mt_u64 t1 = __builtin_amdgcn_s_memtime();
-    const mt_u64 rt1 = __builtin_amdgcn_s_memrealtime();
-    __builtin_amdgcn_sched_barrier(0);
+    const ms_clock t1 = ms_stamp();
     {
         mt_u64 sum = 0;
 #pragma unroll
@@ -503,14 +496,8 @@ valu_sweep_kernel(na_valu_record* __restrict__ records, mt_u64 base, int iters) 
     if (l == 0) {
         na_valu_record rec;
         for (int p = 0; p < VS_PHASES; ++p) rec.checksum[p] = c[p];
-        rec.cycles = t1 - t0;
-        rec.realtime = rt1 - rt0;
         rec.wave = (uint32_t)w;
-        rec.xcc = xcc_id & 15;
-        rec.se = (hw_id >> 13) & 3;
-        rec.sh = (hw_id >> 12) & 1;
-        rec.cu = (hw_id >> 8) & 15;
-        rec.simd = (hw_id >> 4) & 3;
+        ms_record_simd(rec, t0, t1, at);
         rec.rf_bad = rf_bad;
         rec.rf_first_slot = rf_bad ? rf_key >> 6 : ~0u;
         rec.rf_first_lane = rf_bad ? rf_key & 63 : ~0u;
