@@ -17,7 +17,7 @@ import ctypes
 import json
 import os
 import sys
-from dataclasses import asdict, dataclass, field
+from dataclasses import asdict, dataclass, field, fields
 
 _LIB_NAME = "libmi355x_nodeagent.so"
 _SEARCH_PATHS = (
@@ -156,6 +156,13 @@ class MemtestAllocError(NodeAgentError):
     """The memtest region could not be allocated (busy GPU) — not a fault."""
 
 
+def _shared_fields(cls, res) -> dict:
+    """The fields that the C result ``res`` and the dataclass ``cls`` share by
+    name, as keyword arguments for ``cls``; a converter adds the few that differ."""
+    names = {f.name for f in fields(cls)}
+    return {name: getattr(res, name) for name, _type in res._fields_ if name in names}
+
+
 class _MemtestResultC(ctypes.Structure):
     _fields_ = [
         ("bytes_tested", ctypes.c_uint64),
@@ -265,8 +272,8 @@ class MfmaSweepResult:
     @classmethod
     def _from_c(cls, dtype: str, res: "_MfmaSweepResultC", tflops: float = 0.0):
         return cls(
-            dtype, res.waves, res.bad_waves, res.units_seen, res.bad_units, res.first_bad_wave,
-            [tuple(res.bad_list[i]) for i in range(res.listed)], res.clock_mhz, tflops,
+            **_shared_fields(cls, res), dtype=dtype, tflops=tflops,
+            bad_simds=[tuple(res.bad_list[i]) for i in range(res.listed)],
         )
 
 
@@ -365,12 +372,11 @@ class LdsSweepResult:
         phase = ""
         if res.first_bad_workgroup != NO_BAD_WORKGROUP:
             phase = (LDS_SWEEP_PHASES + ("index",))[min(res.first_bad_phase, len(LDS_SWEEP_PHASES))]
-        return cls(
-            res.workgroups, res.bad_workgroups, res.units_seen, res.bad_units,
-            res.first_bad_workgroup, phase, res.bad_words, res.first_bad_offset, res.xor_mask,
-            [tuple(res.bad_list[i]) for i in range(res.listed)], res.clock_mhz,
-            res.median_bytes_per_clk, res.min_bytes_per_clk, res.max_bytes_per_clk, gbs,
-        )
+        # first_bad_phase is a code in C and a name here
+        return cls(**{
+            **_shared_fields(cls, res), "first_bad_phase": phase, "gbs": gbs,
+            "bad_cus": [tuple(res.bad_list[i]) for i in range(res.listed)],
+        })
 
 
 class ValuRecord(ctypes.Structure):
@@ -481,12 +487,9 @@ class ValuSweepResult:
             row = list(res.bad_list[i])
             phases = [n for p, n in enumerate(VALU_SWEEP_MASK_NAMES) if row[6] >> p & 1]
             bad.append((row[0], tuple(row[1:6]), phases))
-        return cls(
-            res.waves, res.bad_waves, res.cus_seen, res.simds_seen, bool(res.trans_unchecked),
-            res.trans_consensus, res.median_cycles, res.clock_mhz, res.median_flop_per_clk,
-            res.min_flop_per_clk, res.tflops, res.rf_bad, res.rf_first_slot, res.rf_first_lane,
-            res.rf_xor, bad,
-        )
+        return cls(**{
+            **_shared_fields(cls, res), "trans_unchecked": bool(res.trans_unchecked), "bad": bad,
+        })
 
 
 def _load_lib() -> ctypes.CDLL:
@@ -564,10 +567,15 @@ class NodeAgent:
     def _err(self) -> str:
         return (self.lib.na_last_error() or b"").decode()
 
+    def _check(self, rc: int, what: str, ok=(NA_OK,)) -> None:
+        """Raise ``NodeAgentError`` with ``what`` and ``na_last_error`` unless
+        the C code ``rc`` is one of ``ok``."""
+        if rc not in ok:
+            raise NodeAgentError(f"{what}: {self._err()}")
+
     def device_count(self) -> int:
         n = ctypes.c_int(0)
-        if self.lib.na_device_count(ctypes.byref(n)) != 0:
-            raise NodeAgentError(f"device_count: {self._err()}")
+        self._check(self.lib.na_device_count(ctypes.byref(n)), "device_count")
         return n.value
 
     def device_info(self, dev: int) -> tuple:
@@ -579,8 +587,7 @@ class NodeAgent:
         rc = self.lib.na_device_info(
             dev, name, 256, arch, 256, ctypes.byref(hbm), ctypes.byref(cus), ctypes.byref(clk)
         )
-        if rc != 0:
-            raise NodeAgentError(f"device_info({dev}): {self._err()}")
+        self._check(rc, f"device_info({dev})")
         return name.value.decode(), arch.value.decode(), hbm.value, cus.value
 
     def hbm_bandwidth(self, dev: int, bytes_: int = 1 << 30, iters: int = 10) -> float:
@@ -588,8 +595,7 @@ class NodeAgent:
         rc = self.lib.na_hbm_bandwidth(
             dev, ctypes.c_longlong(bytes_), iters, ctypes.byref(out)
         )
-        if rc != 0:
-            raise NodeAgentError(f"hbm_bandwidth({dev}): {self._err()}")
+        self._check(rc, f"hbm_bandwidth({dev})")
         return out.value
 
     def fma_selftest(self, dev: int) -> bool:
@@ -641,16 +647,24 @@ class NodeAgent:
         """Launch the one wave of check ``kind`` (a key of ``MFMA_CHECK_KINDS``)
         and return its raw words as a ctypes array of 1024 uint32, of which
         the kind's first 256 (all 1024 for ``bf16_tile32``) are written."""
-        words = (ctypes.c_uint32 * MFMA_CHECK_MAX_WORDS)()
-        rc = self.lib.na_mfma_check_run(dev, MFMA_CHECK_KINDS[kind], words, len(words))
-        if rc != NA_OK:
-            raise NodeAgentError(f"mfma_check_run({dev}, {kind}): {self._err()}")
-        return words
+        return self._check_run("mfma", MFMA_CHECK_KINDS, dev, kind)
 
     def mfma_check_verify(self, kind: str, words) -> int:
         """Compare a kind's words with the exact host reference (needs no GPU).
         Returns the C code; on ``NA_ERR_VERIFY`` ``na_last_error`` names the word."""
-        return self.lib.na_mfma_check_verify(MFMA_CHECK_KINDS[kind], words, len(words))
+        return self._check_verify("mfma", MFMA_CHECK_KINDS, kind, words)
+
+    # The single-wave checks' two families, "mfma" and "mx", differ in symbol
+    # prefix and kind table.
+
+    def _check_run(self, fam: str, kinds: dict, dev: int, kind: str):
+        words = (ctypes.c_uint32 * MFMA_CHECK_MAX_WORDS)()
+        rc = getattr(self.lib, f"na_{fam}_check_run")(dev, kinds[kind], words, len(words))
+        self._check(rc, f"{fam}_check_run({dev}, {kind})")
+        return words
+
+    def _check_verify(self, fam: str, kinds: dict, kind: str, words) -> int:
+        return getattr(self.lib, f"na_{fam}_check_verify")(kinds[kind], words, len(words))
 
     # -- single-wave MX checks ------------------------------------------------
 
@@ -658,8 +672,8 @@ class NodeAgent:
         """Value of ``code`` in format ``fmt`` (a key of ``MX_FORMATS``), by
         the decoder the host references use (needs no GPU)."""
         out = ctypes.c_float(0)
-        if self.lib.na_mx_decode(MX_FORMATS[fmt], code, ctypes.byref(out)) != NA_OK:
-            raise NodeAgentError(f"mx_decode({fmt}, {code}): {self._err()}")
+        rc = self.lib.na_mx_decode(MX_FORMATS[fmt], code, ctypes.byref(out))
+        self._check(rc, f"mx_decode({fmt}, {code})")
         return out.value
 
     def mx_pack(self, fmt: str, codes) -> list:
@@ -670,8 +684,7 @@ class NodeAgent:
         words = (ctypes.c_uint32 * max(n * MX_FORMAT_BITS[fmt] // 32, 1))()
         rc = self.lib.na_mx_pack(MX_FORMATS[fmt], (ctypes.c_int * max(n, 1))(*codes), n, words,
                                  len(words))
-        if rc != NA_OK:
-            raise NodeAgentError(f"mx_pack({fmt}): {self._err()}")
+        self._check(rc, f"mx_pack({fmt})")
         return list(words)
 
     def mx_check_run(self, dev: int, kind: str):
@@ -679,16 +692,12 @@ class NodeAgent:
         ``MX_CHECK_KINDS``) and return its raw words as a ctypes array of
         1024 uint32, of which the kind's first 256 (all 1024 for ``fp4_32``)
         are written: float32 bit patterns."""
-        words = (ctypes.c_uint32 * MFMA_CHECK_MAX_WORDS)()
-        rc = self.lib.na_mx_check_run(dev, MX_CHECK_KINDS[kind], words, len(words))
-        if rc != NA_OK:
-            raise NodeAgentError(f"mx_check_run({dev}, {kind}): {self._err()}")
-        return words
+        return self._check_run("mx", MX_CHECK_KINDS, dev, kind)
 
     def mx_check_verify(self, kind: str, words) -> int:
         """Compare a kind's words with the exact host reference (needs no GPU).
         Returns the C code; on ``NA_ERR_VERIFY`` ``na_last_error`` names the word."""
-        return self.lib.na_mx_check_verify(MX_CHECK_KINDS[kind], words, len(words))
+        return self._check_verify("mx", MX_CHECK_KINDS, kind, words)
 
     def mx_checks(self, dev: int) -> bool:
         """Every kind of ``MX_CHECK_KINDS`` in turn, one wave each, stopping at
@@ -713,8 +722,7 @@ class NodeAgent:
         """D2D copy through the SDMA engines — RCCL's xGMI transport hardware."""
         out = ctypes.c_double(0)
         rc = self.lib.na_sdma_bandwidth(dev, ctypes.c_longlong(bytes_), iters, ctypes.byref(out))
-        if rc != 0:
-            raise NodeAgentError(f"sdma_bandwidth({dev}): {self._err()}")
+        self._check(rc, f"sdma_bandwidth({dev})")
         return out.value
 
     # -- HBM data integrity --------------------------------------------------
@@ -723,8 +731,8 @@ class NodeAgent:
         """(free_bytes, total_bytes) of device memory right now."""
         free = ctypes.c_longlong(0)
         total = ctypes.c_longlong(0)
-        if self.lib.na_mem_info(dev, ctypes.byref(free), ctypes.byref(total)) != NA_OK:
-            raise NodeAgentError(f"mem_info({dev}): {self._err()}")
+        rc = self.lib.na_mem_info(dev, ctypes.byref(free), ctypes.byref(total))
+        self._check(rc, f"mem_info({dev})")
         return free.value, total.value
 
     def memtest_fill(self, dev: int, ptr: int, bytes_: int,
@@ -750,9 +758,7 @@ class NodeAgent:
         )
         if rc not in (NA_OK, NA_ERR_VERIFY):
             return rc, MemtestResult()
-        return rc, MemtestResult(
-            res.bytes_tested, res.bad_words, res.first_bad_offset, res.xor_mask
-        )
+        return rc, MemtestResult(**_shared_fields(MemtestResult, res))
 
     def hbm_memtest(self, dev: int, bytes_: int, rounds: int = 1,
                     seed: int = DEFAULT_MEMTEST_SEED) -> MemtestResult:
@@ -776,9 +782,7 @@ class NodeAgent:
             err = self._err()
             cls = MemtestAllocError if "allocation failed" in err else NodeAgentError
             raise cls(f"hbm_memtest({dev}): {err}")
-        return MemtestResult(
-            res.bytes_tested, res.bad_words, res.first_bad_offset, res.xor_mask, gbs.value
-        )
+        return MemtestResult(**_shared_fields(MemtestResult, res), gbs=gbs.value)
 
     def _run_memtest(self, g: GPUReport, memtest_bytes: int) -> None:
         free, _total = self.mem_info(g.index)
@@ -809,8 +813,7 @@ class NodeAgent:
         ms = ctypes.c_double(0)
         dev = args[0]
         rc = getattr(self.lib, f"na_{what}")(*args, recs, ctypes.c_longlong(n), ctypes.byref(ms))
-        if rc != NA_OK:
-            raise NodeAgentError(f"{what}({dev}): {self._err()}")
+        self._check(rc, f"{what}({dev})")
         return recs, ms.value
 
     def _sweep_verify(self, what, recs, args, res, wrap, empty) -> tuple:
@@ -838,8 +841,7 @@ class NodeAgent:
         rc = getattr(self.lib, f"na_{fam}_sweep_expected")(
             ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
         )
-        if rc != NA_OK:
-            raise NodeAgentError(f"{fam}_sweep_expected: {self._err()}")
+        self._check(rc, f"{fam}_sweep_expected")
         return out.value
 
     def _matrix_sweep_run(self, fam, dev, name, workgroups, outer, seed) -> tuple:
@@ -861,8 +863,7 @@ class NodeAgent:
             dev, self._matrix_code(fam, name), workgroups, outer, ctypes.c_ulonglong(seed),
             ctypes.byref(res), ctypes.byref(tflops),
         )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            raise NodeAgentError(f"{fam}_sweep({dev}, {name}): {self._err()}")
+        self._check(rc, f"{fam}_sweep({dev}, {name})", (NA_OK, NA_ERR_VERIFY))
         return MfmaSweepResult._from_c(name, res, tflops.value)
 
     # -- chip-wide matrix-core sweep ------------------------------------------
@@ -962,8 +963,8 @@ class NodeAgent:
         ``lds_bytes`` is 0: the device's per-workgroup maximum, at most
         160 KiB."""
         out = ctypes.c_longlong(0)
-        if self.lib.na_lds_sweep_allocation(dev, ctypes.byref(out)) != NA_OK:
-            raise NodeAgentError(f"lds_sweep_allocation({dev}): {self._err()}")
+        rc = self.lib.na_lds_sweep_allocation(dev, ctypes.byref(out))
+        self._check(rc, f"lds_sweep_allocation({dev})")
         return out.value
 
     def lds_sweep_expected(self, workgroup: int, lds_bytes: int, iters: int,
@@ -977,8 +978,7 @@ class NodeAgent:
             ctypes.c_ulonglong(seed), ctypes.c_ulonglong(workgroup), ctypes.c_longlong(lds_bytes),
             iters, out, len(out),
         )
-        if rc != NA_OK:
-            raise NodeAgentError(f"lds_sweep_expected: {self._err()}")
+        self._check(rc, "lds_sweep_expected")
         return list(out)
 
     def lds_sweep_run(self, dev: int, workgroups: int = 1, lds_bytes: int = 0, iters: int = 1,
@@ -1020,8 +1020,7 @@ class NodeAgent:
             dev, workgroups, ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed),
             ctypes.byref(res), ctypes.byref(gbs),
         )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            raise NodeAgentError(f"lds_sweep({dev}): {self._err()}")
+        self._check(rc, f"lds_sweep({dev})", (NA_OK, NA_ERR_VERIFY))
         return LdsSweepResult._from_c(res, gbs.value)
 
     def _run_lds_sweep(self, g: GPUReport) -> None:
@@ -1063,8 +1062,7 @@ class NodeAgent:
         rc = self.lib.na_valu_sweep_expected(
             ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), iters, out
         )
-        if rc != NA_OK:
-            raise NodeAgentError(f"valu_sweep_expected: {self._err()}")
+        self._check(rc, "valu_sweep_expected")
         return list(out)
 
     def valu_sweep_run(self, dev: int, workgroups: int = 1, iters: int = 1,
@@ -1102,8 +1100,7 @@ class NodeAgent:
         rc = self.lib.na_valu_sweep(
             dev, workgroups, iters, ctypes.c_ulonglong(seed), ctypes.byref(res)
         )
-        if rc not in (NA_OK, NA_ERR_VERIFY):
-            raise NodeAgentError(f"valu_sweep({dev}): {self._err()}")
+        self._check(rc, f"valu_sweep({dev})", (NA_OK, NA_ERR_VERIFY))
         return ValuSweepResult._from_c(res)
 
     def _run_valu_sweep(self, g: GPUReport) -> None:
@@ -1122,8 +1119,7 @@ class NodeAgent:
 
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
-        if self.lib.na_p2p_matrix(n, buf) != 0:
-            raise NodeAgentError(f"p2p_matrix: {self._err()}")
+        self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
         return [[buf[i * n + j] for j in range(n)] for i in range(n)]
 
     def p2p_bandwidth(self, src: int, dst: int, bytes_: int = 256 << 20, iters: int = 5) -> float:
@@ -1131,8 +1127,7 @@ class NodeAgent:
         rc = self.lib.na_p2p_bandwidth(
             src, dst, ctypes.c_longlong(bytes_), iters, ctypes.byref(out)
         )
-        if rc != 0:
-            raise NodeAgentError(f"p2p_bandwidth({src},{dst}): {self._err()}")
+        self._check(rc, f"p2p_bandwidth({src},{dst})")
         return out.value
 
     # -- full health check ---------------------------------------------------

@@ -12,7 +12,9 @@
 // mfma_frag.h, run and verified by na_mfma_check_run / _verify), an opt-in
 // chip-wide matrix-core sweep (one wave per SIMD of every CU, mfmasweep.h),
 // opt-in single-wave checks and the same sweep on the block-scaled MX
-// instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h), an
+// instructions in fp4/fp6/bf6/bf8 (na_mx_*, formats in mx_formats.h; both
+// families of single-wave checks are rows of one table type with one
+// argument check, run and verify: check_run / check_verify), an
 // opt-in chip-wide LDS sweep (every LDS access path on every CU, ldssweep.h),
 // an opt-in chip-wide vector-unit sweep (register file and VALU of every
 // SIMD, valusweep.h), and the xGMI peer-to-peer link matrix. The three
@@ -37,34 +39,35 @@
 
 #include "memtest.h"
 #include "mfma_frag.h"
+#include "sweep_common.h"
 
 #define NA_OK 0
 #define NA_ERR_HIP -1
 #define NA_ERR_VERIFY -2
 #define NA_ERR_ARG -3
 
-#define HIP_CHECK(expr)                                                                  \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                          \
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s at %s:%d",   \
-                          hipGetErrorString(_e), __FILE__, __LINE__);                    \
-            return NA_ERR_HIP;                                                           \
-        }                                                                                \
-    } while (0)
-
 static char na_last_error_buf[512];
 
 extern "C" const char* na_last_error() { return na_last_error_buf; }
 
-// Every argument error: the message into na_last_error, NA_ERR_ARG back.
-__attribute__((format(printf, 1, 2))) static int arg_error(const char* fmt, ...) {
+// Every error report: the message into na_last_error, `rc` back.
+__attribute__((format(printf, 2, 3))) static int na_error(int rc, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     std::vsnprintf(na_last_error_buf, sizeof(na_last_error_buf), fmt, ap);
     va_end(ap);
-    return NA_ERR_ARG;
+    return rc;
 }
+
+#define arg_error(...) na_error(NA_ERR_ARG, __VA_ARGS__)
+
+#define HIP_CHECK(expr)                                                                  \
+    do {                                                                                 \
+        hipError_t _e = (expr);                                                          \
+        if (_e != hipSuccess)                                                            \
+            return na_error(NA_ERR_HIP, "%s at %s:%d", hipGetErrorString(_e), __FILE__,  \
+                            __LINE__);                                                   \
+    } while (0)
 
 // ---------------------------------------------------------------------------
 // HIP resources: HIP_CHECK returns from the middle of a function, so whatever
@@ -319,29 +322,51 @@ extern "C" int na_device_info(int dev, char* name, int name_len, char* arch, int
     return NA_OK;
 }
 
+// The second of a bandwidth probe's two buffers: n elements, a failure
+// reported by the runtime's message alone.
+template <typename T>
+static int alloc_second(dev_buf<T>& buf, size_t n) {
+    hipError_t e = buf.alloc(n);
+    return e == hipSuccess ? NA_OK : na_error(NA_ERR_HIP, "%s", hipGetErrorString(e));
+}
+
+// The timed loop of the bandwidth probes: op() once as warm-up, then `iters`
+// times between two events on `stream`; *ms is the time between the events.
+// The null stream synchronises the device after the warm-up, any other
+// stream itself. An event of `t` the caller has not created is created after
+// the warm-up.
+template <typename OP>
+static int timed_loop(hipStream_t stream, int iters, dev_events<2>& t, float* ms, OP op) {
+    HIP_CHECK(op());
+    HIP_CHECK(stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize());
+    for (hipEvent_t& e : t.e)
+        if (!e) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(t.e[0], stream));
+    for (int i = 0; i < iters; ++i) HIP_CHECK(op());
+    HIP_CHECK(hipEventRecord(t.e[1], stream));
+    HIP_CHECK(hipEventSynchronize(t.e[1]));
+    HIP_CHECK(hipEventElapsedTime(ms, t.e[0], t.e[1]));
+    return NA_OK;
+}
+
 extern "C" int na_hbm_bandwidth(int dev, long long bytes, int iters, double* gbs) {
     HIP_CHECK(hipSetDevice(dev));
     size_t n = (size_t)bytes / sizeof(float4);
     dev_buf<float4> src, dst;
     HIP_CHECK(src.alloc(n));
-    hipError_t e2 = dst.alloc(n);
-    if (e2 != hipSuccess) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s", hipGetErrorString(e2));
-        return NA_ERR_HIP;
-    }
+    int rc = alloc_second(dst, n);
+    if (rc != NA_OK) return rc;
     HIP_CHECK(hipMemset(src.p, 1, n * sizeof(float4)));
     // sweep winner: 16384 WGs × 1024 threads, 4-deep in-chunk unroll
     dim3 grid(16384), block(1024);
     dev_events<2> t;
     for (hipEvent_t& e : t.e) HIP_CHECK(hipEventCreate(&e));
-    copy_f4_kernel<<<grid, block>>>(src.p, dst.p, n);  // warmup
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipEventRecord(t.e[0]));
-    for (int i = 0; i < iters; ++i) copy_f4_kernel<<<grid, block>>>(src.p, dst.p, n);
-    HIP_CHECK(hipEventRecord(t.e[1]));
-    HIP_CHECK(hipEventSynchronize(t.e[1]));
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t.e[0], t.e[1]));
+    rc = timed_loop(nullptr, iters, t, &ms, [&] {
+        copy_f4_kernel<<<grid, block>>>(src.p, dst.p, n);
+        return hipSuccess;  // the launches go unqueried, so nothing sits between two of them
+    });
+    if (rc != NA_OK) return rc;
     // read + write
     *gbs = (2.0 * (double)bytes * iters) / (ms * 1e6);
     return NA_OK;
@@ -358,113 +383,173 @@ extern "C" int na_fma_selftest(int dev) {
     HIP_CHECK(hipMemcpy(host.data(), out.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int i = 0; i < blocks * threads; ++i) {
         // fixpoint of x -> x/2 + 1/4 is 0.5; 256 iterations converge exactly
-        if (host[i] != 0.5f) {
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "fma selftest: lane %d got %g want 0.5", i, host[i]);
-            return NA_ERR_VERIFY;
-        }
+        if (host[i] != 0.5f)
+            return na_error(NA_ERR_VERIFY, "fma selftest: lane %d got %g want 0.5", i, host[i]);
     }
     return NA_OK;
 }
 
-// One wave of a check kernel; its `words` raw 32-bit words go to out.
-static int check_launch(int dev, void (*kernel)(void*, int), int scale_a, void* out, int words) {
-    HIP_CHECK(hipSetDevice(dev));
-    dev_buf<uint32_t> d;
-    HIP_CHECK(d.alloc((size_t)words));
-    kernel<<<dim3(1), dim3(64)>>>(d.p, scale_a);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, d.p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return NA_OK;
-}
+// How a single-wave check's wanted D[i][j] comes about.
+enum check_want {
+    WANT_UNIFORM,   // the constant 2*K*alpha*beta (alpha*beta = 3)
+    WANT_TILE,      // `mult` times the integer product of tile_a and tile_b
+    WANT_MX_TILE,   // the block-scaled sum of mx_tile_operands
+    WANT_MX_CODES,  // the code-point sum of mx_code_operands over format `code_fmt`
+};
 
-// One row per kind of the single-wave MFMA checks (mfma_frag.h), in the
-// order of the kind codes. `label` opens the failure message. D of the MX
-// kinds is `mult` times the unscaled product.
-struct mfma_check {
+// One row per kind of the single-wave checks, of both families: the NA_MFMA_*
+// kinds and the NA_MX_* kinds of mfma_frag.h. `label` opens the failure
+// message. The words are int32 for the i8 kind (`is_int`), float32 otherwise.
+struct wave_check {
     const char* label;
     void (*kernel)(void*, int);
-    int mn, k, scale_a, mult;
-    bool uniform, is_int;
+    int mn, k, scale_a;
+    bool is_int;
+    check_want want;
+    int mult, code_fmt;
     int words() const { return mn * mn; }  // 64 lanes x 4 registers for the uniform kinds too
 };
 
 template <typename T, typename GEN>
-static mfma_check mfma_check_row(const char* label, int scale_a = 0, int mult = 1) {
-    return {label, mfma_check_kernel<T, GEN>, T::MN, T::K, scale_a, mult, GEN::UNIFORM != 0,
-            std::is_same<typename T::word, int>::value};
+static wave_check check_row(const char* label, check_want want, int scale_a = 0, int mult = 1,
+                            int code_fmt = -1) {
+    return {label, mfma_check_kernel<T, GEN>, T::MN, T::K, scale_a,
+            std::is_same<typename T::word, int>::value, want, mult, code_fmt};
+}
+template <typename T>
+static wave_check mx_tile_row(const char* label) {
+    return check_row<T, mx_tile_operands>(label, WANT_MX_TILE);
+}
+template <int FMT, int OA, int OB>
+static wave_check mx_code_row(const char* label) {
+    typedef mfma_mxs_16x16x128<FMT, MX_E2M1, OA, OB> T;
+    return check_row<T, mx_code_operands>(label, WANT_MX_CODES, 0, 1, FMT);
 }
 
-static const mfma_check mfma_checks[NA_MFMA_KINDS] = {
-    mfma_check_row<mfma_f32_16x16x4, uniform_operands>("mfma selftest"),
-    mfma_check_row<mfma_bf16_16x16x32, uniform_operands>("mfma-bf16 selftest"),
-    mfma_check_row<mfma_fp8_16x16x32, uniform_operands>("mfma-fp8 selftest"),
-    mfma_check_row<mfma_bf16_16x16x32, tile_operands>("mfma bf16 tile"),
-    mfma_check_row<mfma_f16_16x16x32, tile_operands>("mfma f16 tile"),
-    mfma_check_row<mfma_fp8_16x16x32, tile_operands>("mfma fp8 tile"),
-    mfma_check_row<mfma_i8_16x16x64, tile_operands>("mfma i8 tile"),
-    mfma_check_row<mfma_bf16_32x32x16, tile_operands>("mfma bf16 32x32 tile"),
-    mfma_check_row<mfma_mx_16x16x128, tile_operands>("mfma mx tile (scale 1x)", 0x7F, 1),
-    mfma_check_row<mfma_mx_16x16x128, tile_operands>("mfma mx tile (scale 2x)", 0x80, 2),
+// In the order of the NA_MFMA_* codes. D of the two MX kinds is `mult` times
+// the unscaled product.
+static const wave_check mfma_checks[NA_MFMA_KINDS] = {
+    check_row<mfma_f32_16x16x4, uniform_operands>("mfma selftest", WANT_UNIFORM),
+    check_row<mfma_bf16_16x16x32, uniform_operands>("mfma-bf16 selftest", WANT_UNIFORM),
+    check_row<mfma_fp8_16x16x32, uniform_operands>("mfma-fp8 selftest", WANT_UNIFORM),
+    check_row<mfma_bf16_16x16x32, tile_operands>("mfma bf16 tile", WANT_TILE),
+    check_row<mfma_f16_16x16x32, tile_operands>("mfma f16 tile", WANT_TILE),
+    check_row<mfma_fp8_16x16x32, tile_operands>("mfma fp8 tile", WANT_TILE),
+    check_row<mfma_i8_16x16x64, tile_operands>("mfma i8 tile", WANT_TILE),
+    check_row<mfma_bf16_32x32x16, tile_operands>("mfma bf16 32x32 tile", WANT_TILE),
+    check_row<mfma_mx_16x16x128, tile_operands>("mfma mx tile (scale 1x)", WANT_TILE, 0x7F, 1),
+    check_row<mfma_mx_16x16x128, tile_operands>("mfma mx tile (scale 2x)", WANT_TILE, 0x80, 2),
 };
 
-static const mfma_check* mfma_check_args(const char* fn, int kind, const void* words,
-                                         int n_words) {
-    if (kind >= 0 && kind < NA_MFMA_KINDS && words != nullptr &&
-        n_words >= mfma_checks[kind].words())
-        return &mfma_checks[kind];
-    arg_error("%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the 32x32 "
+// In the order of the NA_MX_* codes. Between them the kinds select every byte
+// of the scale register on each side.
+static const wave_check mx_checks[NA_MX_KINDS] = {
+    mx_tile_row<mfma_mxs_16x16x128<MX_E2M1, MX_E2M1, 1, 2>>("mx fp4 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E2M3, MX_E2M3, 2, 3>>("mx fp6 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E3M2, MX_E3M2, 3, 0>>("mx bf6 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E5M2, MX_E5M2, 0, 1>>("mx bf8 tile"),
+    mx_tile_row<mfma_mxs_16x16x128<MX_E4M3, MX_E2M1, 2, 1>>("mx fp8 x fp4 tile"),
+    mx_tile_row<mfma_mxs_32x32x64<MX_E2M1, MX_E2M1, 3, 2>>("mx fp4 32x32 tile"),
+    mx_code_row<MX_E2M1, 1, 3>("mx fp4 codes"),
+    mx_code_row<MX_E2M3, 3, 1>("mx fp6 codes"),
+    mx_code_row<MX_E3M2, 2, 2>("mx bf6 codes"),
+};
+
+// A family's table; `prefix` opens its argument errors.
+struct check_family {
+    const char* prefix;
+    const wave_check* rows;
+    int kinds;
+};
+static const check_family mfma_family = {"na_mfma_check", mfma_checks, NA_MFMA_KINDS};
+static const check_family mx_family = {"na_mx_check", mx_checks, NA_MX_KINDS};
+
+// Every value is a small integer or a multiple of 1/4 below 2^13: exact in
+// float, and every partial sum with it.
+static float check_want_at(const wave_check& c, int i, int j) {
+    float want = 0.f;
+    switch (c.want) {
+        case WANT_UNIFORM: return (float)(2 * c.k * 3);
+        case WANT_TILE: {
+            int dot = 0;
+            for (int k = 0; k < c.k; ++k) dot += tile_a(i, k % 64) * tile_b(k % 64, j);
+            return (float)(dot * c.mult);
+        }
+        case WANT_MX_TILE:
+            for (int blk = 0; blk < c.k / 32; ++blk) {
+                int dot = 0;
+                for (int k = blk * 32; k < blk * 32 + 32; ++k)
+                    dot += mx_tile_a(i, k) * mx_tile_b(k, j);
+                want += std::ldexp((float)dot, mx_tile_ea(i, blk) + mx_tile_eb(blk, j));
+            }
+            return want;
+        case WANT_MX_CODES:
+            for (int m = 0; m < c.k / 16; ++m)
+                want += mx_decode(c.code_fmt, mx_code_a(c.code_fmt, i, j + 16 * m));
+            return want;
+    }
+    return want;
+}
+
+static const wave_check* check_args(const check_family& fam, const char* fn, int kind,
+                                    const void* words, int n_words) {
+    if (kind >= 0 && kind < fam.kinds && words != nullptr && n_words >= fam.rows[kind].words())
+        return &fam.rows[kind];
+    arg_error("%s_%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the 32x32 "
               "tile (words %p, n_words %d)",
-              fn, NA_MFMA_KINDS - 1, kind, words, n_words);
+              fam.prefix, fn, fam.kinds - 1, kind, words, n_words);
     return nullptr;
 }
 
-// Launches the one wave of `kind` and copies its raw 32-bit words back:
-// int32 for the i8 kind, float32 otherwise. Argument errors are detected
-// before any HIP call.
-extern "C" int na_mfma_check_run(int dev, int kind, void* out, int n_words) {
-    const mfma_check* c = mfma_check_args("na_mfma_check_run", kind, out, n_words);
+// Launches the one wave of `kind` and copies its raw 32-bit words back.
+// Argument errors are detected before any HIP call.
+static int check_run(const check_family& fam, int dev, int kind, void* out, int n_words) {
+    const wave_check* c = check_args(fam, "run", kind, out, n_words);
     if (c == nullptr) return NA_ERR_ARG;
-    return check_launch(dev, c->kernel, c->scale_a, out, c->words());
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<uint32_t> d;
+    HIP_CHECK(d.alloc((size_t)c->words()));
+    c->kernel<<<dim3(1), dim3(64)>>>(d.p, c->scale_a);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, d.p, (size_t)c->words() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NA_OK;
 }
 
 // Pure host code: compares the words of `kind` by value against the exact
-// reference, the constant 2*K*alpha*beta (alpha*beta = 3) for the uniform
-// kinds and the row-major integer product of the tile operands otherwise.
-// The first mismatch is named in na_last_error.
-extern "C" int na_mfma_check_verify(int kind, const void* words, int n_words) {
-    const mfma_check* c = mfma_check_args("na_mfma_check_verify", kind, words, n_words);
+// reference. The first mismatch is named in na_last_error.
+static int check_verify(const check_family& fam, int kind, const void* words, int n_words) {
+    const wave_check* c = check_args(fam, "verify", kind, words, n_words);
     if (c == nullptr) return NA_ERR_ARG;
     const float* f = static_cast<const float*>(words);
     const int* w = static_cast<const int*>(words);
     for (int e = 0; e < c->words(); ++e) {
         const int i = e / c->mn, j = e % c->mn;
-        int want = 2 * c->k * 3;
-        if (!c->uniform) {
-            want = 0;
-            for (int k = 0; k < c->k; ++k) want += tile_a(i, k % 64) * tile_b(k % 64, j);
-            want *= c->mult;
-        }
-        if (c->is_int ? w[e] == want : f[e] == (float)want) continue;
-        if (c->uniform)
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "%s: elem %d got %g want %g", c->label, e, f[e], (float)want);
-        else if (c->is_int)
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "%s: D[%d][%d] got %d want %d", c->label, i, j, w[e], want);
-        else
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "%s: D[%d][%d] got %g want %g", c->label, i, j, f[e], (float)want);
-        return NA_ERR_VERIFY;
+        const float want = check_want_at(*c, i, j);
+        if (c->is_int ? w[e] == (int)want : f[e] == want) continue;
+        if (c->want == WANT_UNIFORM)
+            return na_error(NA_ERR_VERIFY, "%s: elem %d got %g want %g", c->label, e, f[e], want);
+        if (c->is_int)
+            return na_error(NA_ERR_VERIFY, "%s: D[%d][%d] got %d want %d", c->label, i, j, w[e],
+                            (int)want);
+        return na_error(NA_ERR_VERIFY, "%s: D[%d][%d] got %g want %g", c->label, i, j, f[e], want);
     }
     return NA_OK;
 }
 
-static int mfma_check_one(int dev, int kind) {
+static int check_one(const check_family& fam, int dev, int kind) {
     uint32_t words[1024];
-    int rc = na_mfma_check_run(dev, kind, words, 1024);
-    return rc != NA_OK ? rc : na_mfma_check_verify(kind, words, 1024);
+    int rc = check_run(fam, dev, kind, words, 1024);
+    return rc != NA_OK ? rc : check_verify(fam, kind, words, 1024);
 }
+
+// The words of an NA_MFMA_* kind are int32 for the i8 kind, float32 otherwise.
+extern "C" int na_mfma_check_run(int dev, int kind, void* out, int n_words) {
+    return check_run(mfma_family, dev, kind, out, n_words);
+}
+extern "C" int na_mfma_check_verify(int kind, const void* words, int n_words) {
+    return check_verify(mfma_family, kind, words, n_words);
+}
+static int mfma_check_one(int dev, int kind) { return check_one(mfma_family, dev, kind); }
 
 extern "C" int na_mfma_selftest(int dev) { return mfma_check_one(dev, NA_MFMA_F32_UNIFORM); }
 extern "C" int na_mfma_bf16_selftest(int dev) { return mfma_check_one(dev, NA_MFMA_BF16_UNIFORM); }
@@ -519,104 +604,40 @@ extern "C" int na_mx_pack(int fmt, const int* codes, int n, uint32_t* words, int
     return NA_OK;
 }
 
-// One row per kind, in the order of the NA_MX_* codes.
-struct mx_check {
-    const char* label;
-    void (*kernel)(void*, int);
-    int mn, k;
-    int code_fmt;  // format whose codes the kind enumerates, -1 for the tile kinds
-    int words() const { return mn * mn; }
-};
-
-template <typename T>
-static mx_check mx_tile_row(const char* label) {
-    return {label, mfma_check_kernel<T, mx_tile_operands>, T::MN, T::K, -1};
-}
-template <int FMT, int OA, int OB>
-static mx_check mx_code_row(const char* label) {
-    typedef mfma_mxs_16x16x128<FMT, MX_E2M1, OA, OB> T;
-    return {label, mfma_check_kernel<T, mx_code_operands>, T::MN, T::K, FMT};
-}
-
-// Between them the kinds select every byte of the scale register on each side.
-static const mx_check mx_checks[NA_MX_KINDS] = {
-    mx_tile_row<mfma_mxs_16x16x128<MX_E2M1, MX_E2M1, 1, 2>>("mx fp4 tile"),
-    mx_tile_row<mfma_mxs_16x16x128<MX_E2M3, MX_E2M3, 2, 3>>("mx fp6 tile"),
-    mx_tile_row<mfma_mxs_16x16x128<MX_E3M2, MX_E3M2, 3, 0>>("mx bf6 tile"),
-    mx_tile_row<mfma_mxs_16x16x128<MX_E5M2, MX_E5M2, 0, 1>>("mx bf8 tile"),
-    mx_tile_row<mfma_mxs_16x16x128<MX_E4M3, MX_E2M1, 2, 1>>("mx fp8 x fp4 tile"),
-    mx_tile_row<mfma_mxs_32x32x64<MX_E2M1, MX_E2M1, 3, 2>>("mx fp4 32x32 tile"),
-    mx_code_row<MX_E2M1, 1, 3>("mx fp4 codes"),
-    mx_code_row<MX_E2M3, 3, 1>("mx fp6 codes"),
-    mx_code_row<MX_E3M2, 2, 2>("mx bf6 codes"),
-};
-
-static float mx_check_want(const mx_check& c, int i, int j) {
-    float want = 0.f;  // every partial sum is exact
-    if (c.code_fmt >= 0) {
-        for (int m = 0; m < c.k / 16; ++m)
-            want += mx_decode(c.code_fmt, mx_code_a(c.code_fmt, i, j + 16 * m));
-        return want;
-    }
-    for (int blk = 0; blk < c.k / 32; ++blk) {
-        int dot = 0;
-        for (int k = blk * 32; k < blk * 32 + 32; ++k) dot += mx_tile_a(i, k) * mx_tile_b(k, j);
-        want += std::ldexp((float)dot, mx_tile_ea(i, blk) + mx_tile_eb(blk, j));
-    }
-    return want;
-}
-
-static const mx_check* mx_check_args(const char* fn, int kind, const void* words, int n_words) {
-    if (kind >= 0 && kind < NA_MX_KINDS && words != nullptr && n_words >= mx_checks[kind].words())
-        return &mx_checks[kind];
-    arg_error("%s: need kind in 0..%d (got %d) and room for its 256 words, 1024 for the 32x32 "
-              "tile (words %p, n_words %d)",
-              fn, NA_MX_KINDS - 1, kind, words, n_words);
-    return nullptr;
-}
-
 // As na_mfma_check_run / na_mfma_check_verify, on the NA_MX_* kinds: every
 // word is a float32.
 extern "C" int na_mx_check_run(int dev, int kind, void* out, int n_words) {
-    const mx_check* c = mx_check_args("na_mx_check_run", kind, out, n_words);
-    if (c == nullptr) return NA_ERR_ARG;
-    return check_launch(dev, c->kernel, 0, out, c->words());
+    return check_run(mx_family, dev, kind, out, n_words);
 }
-
 extern "C" int na_mx_check_verify(int kind, const void* words, int n_words) {
-    const mx_check* c = mx_check_args("na_mx_check_verify", kind, words, n_words);
-    if (c == nullptr) return NA_ERR_ARG;
-    const float* f = static_cast<const float*>(words);
-    for (int e = 0; e < c->words(); ++e) {
-        const int i = e / c->mn, j = e % c->mn;
-        const float want = mx_check_want(*c, i, j);
-        if (f[e] == want) continue;
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "%s: D[%d][%d] got %g want %g", c->label, i, j, f[e], want);
-        return NA_ERR_VERIFY;
-    }
-    return NA_OK;
+    return check_verify(mx_family, kind, words, n_words);
 }
 
 // Every kind in turn, stopping at the first that fails.
 extern "C" int na_mx_checks(int dev) {
-    uint32_t words[1024];
     for (int kind = 0; kind < NA_MX_KINDS; ++kind) {
-        int rc = na_mx_check_run(dev, kind, words, 1024);
-        if (rc == NA_OK) rc = na_mx_check_verify(kind, words, 1024);
+        int rc = check_one(mx_family, dev, kind);
         if (rc != NA_OK) return rc;
     }
     return NA_OK;
 }
 
-extern "C" int na_lds_selftest(int dev, long long* bytes_tested) {
-    HIP_CHECK(hipSetDevice(dev));
+// The device's whole per-workgroup LDS allocation (160 KiB/CU on gfx950, minus
+// any runtime-reserved slice reported via sharedMemPerBlock): what
+// na_lds_selftest tests and the dynamic LDS the sweep kernels are launched
+// with. It is more than half of the CU's LDS, so one workgroup per CU.
+static int sweep_lds_bytes(int dev, size_t* bytes) {
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    // whole per-WG LDS allocation (160 KiB/CU on gfx950, minus any
-    // runtime-reserved slice reported via sharedMemPerBlock)
-    size_t lds_bytes = prop.sharedMemPerBlock;
-    if (lds_bytes > 160 * 1024) lds_bytes = 160 * 1024;
+    *bytes = std::min<size_t>(prop.sharedMemPerBlock, MS_CU_LDS_BYTES);
+    return NA_OK;
+}
+
+extern "C" int na_lds_selftest(int dev, long long* bytes_tested) {
+    HIP_CHECK(hipSetDevice(dev));
+    size_t lds_bytes = 0;
+    int rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
     size_t words = lds_bytes / sizeof(unsigned);
     dev_buf<unsigned> fails;
     HIP_CHECK(fails.alloc(1));
@@ -624,20 +645,14 @@ extern "C" int na_lds_selftest(int dev, long long* bytes_tested) {
     // 2048 WGs: every CU's LDS array gets exercised multiple times
     lds_selftest_kernel<<<dim3(2048), dim3(256), lds_bytes>>>(fails.p, words);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "lds launch: %s",
-                      hipGetErrorString(e));
-        return NA_ERR_HIP;
-    }
+    if (e != hipSuccess) return na_error(NA_ERR_HIP, "lds launch: %s", hipGetErrorString(e));
     HIP_CHECK(hipDeviceSynchronize());
     unsigned bad = 0;
     HIP_CHECK(hipMemcpy(&bad, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (bytes_tested) *bytes_tested = (long long)lds_bytes;
-    if (bad) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                      "lds selftest: %u mismatched words across %zu-byte LDS", bad, lds_bytes);
-        return NA_ERR_VERIFY;
-    }
+    if (bad)
+        return na_error(NA_ERR_VERIFY, "lds selftest: %u mismatched words across %zu-byte LDS", bad,
+                        lds_bytes);
     return NA_OK;
 }
 
@@ -649,26 +664,17 @@ extern "C" int na_sdma_bandwidth(int dev, long long bytes, int iters, double* gb
     HIP_CHECK(hipSetDevice(dev));
     dev_buf<char> src, dst;
     HIP_CHECK(src.alloc((size_t)bytes));
-    hipError_t e2 = dst.alloc((size_t)bytes);
-    if (e2 != hipSuccess) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s", hipGetErrorString(e2));
-        return NA_ERR_HIP;
-    }
+    int rc = alloc_second(dst, (size_t)bytes);
+    if (rc != NA_OK) return rc;
     HIP_CHECK(hipMemset(src.p, 7, (size_t)bytes));
     dev_stream stream;
     HIP_CHECK(hipStreamCreate(&stream.s));
-    // warmup
-    HIP_CHECK(hipMemcpyAsync(dst.p, src.p, (size_t)bytes, hipMemcpyDeviceToDevice, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    dev_events<2> t;
-    for (hipEvent_t& e : t.e) HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(t.e[0], stream.s));
-    for (int i = 0; i < iters; ++i)
-        HIP_CHECK(hipMemcpyAsync(dst.p, src.p, (size_t)bytes, hipMemcpyDeviceToDevice, stream.s));
-    HIP_CHECK(hipEventRecord(t.e[1], stream.s));
-    HIP_CHECK(hipEventSynchronize(t.e[1]));
+    dev_events<2> t;  // created by timed_loop
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t.e[0], t.e[1]));
+    rc = timed_loop(stream.s, iters, t, &ms, [&] {
+        return hipMemcpyAsync(dst.p, src.p, (size_t)bytes, hipMemcpyDeviceToDevice, stream.s);
+    });
+    if (rc != NA_OK) return rc;
     *gbs = (2.0 * (double)bytes * iters) / (ms * 1e6);  // read + write
     return NA_OK;
 }
@@ -695,23 +701,16 @@ extern "C" int na_p2p_bandwidth(int src, int dst, long long bytes, int iters, do
     dev_buf<char> sbuf(src), dbuf(dst);
     HIP_CHECK(sbuf.alloc((size_t)bytes));
     HIP_CHECK(hipSetDevice(dst));
-    hipError_t e = dbuf.alloc((size_t)bytes);
-    if (e != hipSuccess) {
-        std::snprintf(na_last_error_buf, sizeof(na_last_error_buf), "%s", hipGetErrorString(e));
-        return NA_ERR_HIP;
-    }
+    int rc = alloc_second(dbuf, (size_t)bytes);
+    if (rc != NA_OK) return rc;
     HIP_CHECK(hipSetDevice(src));
     dev_events<2> t;
     for (hipEvent_t& ev : t.e) HIP_CHECK(hipEventCreate(&ev));
-    HIP_CHECK(hipMemcpyPeer(dbuf.p, dst, sbuf.p, src, (size_t)bytes));  // warmup
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipEventRecord(t.e[0]));
-    for (int i = 0; i < iters; ++i)
-        HIP_CHECK(hipMemcpyPeer(dbuf.p, dst, sbuf.p, src, (size_t)bytes));
-    HIP_CHECK(hipEventRecord(t.e[1]));
-    HIP_CHECK(hipEventSynchronize(t.e[1]));
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t.e[0], t.e[1]));
+    rc = timed_loop(nullptr, iters, t, &ms, [&] {
+        return hipMemcpyPeer(dbuf.p, dst, sbuf.p, src, (size_t)bytes);
+    });
+    if (rc != NA_OK) return rc;
     *gbs = ((double)bytes * iters) / (ms * 1e6);
     return NA_OK;
 }
@@ -751,16 +750,14 @@ static int mt_launch(int mode, void* dptr, size_t nvec, mt_u64 v0, mt_u64 seed, 
                      mt_accum* d_acc) {
     const mt_u64 base = seed * 0x9E3779B97F4A7C15ULL;
     const mt_u64 inv = invert ? ~0ULL : 0ULL;
+    // indexed by the MT_* mode
+    static void (*const kernels[3])(mt_vec*, size_t, mt_u64, mt_u64, mt_u64, mt_accum*) = {
+        memtest_kernel<MT_FILL>, memtest_kernel<MT_VERIFY>, memtest_kernel<MT_VERIFY_FLIP>};
     for (size_t off = 0; off < nvec; off += MT_MAX_LAUNCH_VECS) {
         size_t n = nvec - off < MT_MAX_LAUNCH_VECS ? nvec - off : MT_MAX_LAUNCH_VECS;
         mt_vec* p = reinterpret_cast<mt_vec*>(dptr) + off;
         dim3 grid((unsigned)((n + MT_TILE - 1) / MT_TILE)), block(MT_BLOCK);
-        if (mode == MT_FILL)
-            memtest_kernel<MT_FILL><<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
-        else if (mode == MT_VERIFY)
-            memtest_kernel<MT_VERIFY><<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
-        else
-            memtest_kernel<MT_VERIFY_FLIP><<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
+        kernels[mode]<<<grid, block>>>(p, n, v0 + off, base, inv, d_acc);
         HIP_CHECK(hipGetLastError());
     }
     return NA_OK;
@@ -796,12 +793,11 @@ static int mt_check_args(const char* fn, const void* dptr, long long bytes) {
 
 static int mt_verdict(const na_memtest_result* r) {
     if (r->bad_words == 0) return NA_OK;
-    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "hbm memtest: %llu bad 64-bit words in %llu bytes, first at offset 0x%llx, "
-                  "failing bits 0x%016llx",
-                  (unsigned long long)r->bad_words, (unsigned long long)r->bytes_tested,
-                  (unsigned long long)r->first_bad_offset, (unsigned long long)r->xor_mask);
-    return NA_ERR_VERIFY;
+    return na_error(NA_ERR_VERIFY,
+                    "hbm memtest: %llu bad 64-bit words in %llu bytes, first at offset 0x%llx, "
+                    "failing bits 0x%016llx",
+                    (unsigned long long)r->bad_words, (unsigned long long)r->bytes_tested,
+                    (unsigned long long)r->first_bad_offset, (unsigned long long)r->xor_mask);
 }
 
 // Pointer-level calls on caller-owned device memory (16-byte aligned,
@@ -861,10 +857,9 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
         hipError_t e = chunks.back().alloc(n);
         if (e != hipSuccess) {
             (void)hipGetLastError();  // consumed here, not by a later check
-            std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                          "hbm memtest: allocation failed after %zu of %lld bytes: %s", off * 16,
-                          bytes, hipGetErrorString(e));
-            return NA_ERR_HIP;
+            return na_error(NA_ERR_HIP,
+                            "hbm memtest: allocation failed after %zu of %lld bytes: %s", off * 16,
+                            bytes, hipGetErrorString(e));
         }
         chunk_vecs.push_back(n);
     }
@@ -930,21 +925,11 @@ extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned lon
 // runs twice and verifies. A sweep owns its reference, its verdict rules, its
 // messages and its argument checks; the launch (sweep_launch), the defaults
 // and the warm-up (sweep_defaults, sweep_twice) and the bookkeeping over the
-// records (sweep_census, median_of) are here, for the next sweep too.
-
-#include "sweep_common.h"
+// records (sweep_census, median_of) are here, for the next sweep too. The
+// LDS size they launch with (sweep_lds_bytes) is further up, with
+// na_lds_selftest, which tests the same allocation.
 
 #define SWEEP_MAX_LISTED 8
-
-// The dynamic LDS the sweep kernels are launched with: the device's whole
-// per-workgroup allocation, as na_lds_selftest launches with. It is more
-// than half of the CU's LDS, so one workgroup per CU.
-static int sweep_lds_bytes(int dev, size_t* bytes) {
-    hipDeviceProp_t prop;
-    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    *bytes = std::min<size_t>(prop.sharedMemPerBlock, MS_CU_LDS_BYTES);
-    return NA_OK;
-}
 
 // What 0 means to the whole-sweep entry points: four workgroups per CU, and
 // the sweep's default count of folds, passes or rounds.
@@ -990,8 +975,9 @@ static int sweep_twice(RUN run) {
 }
 
 // 0 for none.
-static double median_of(std::vector<double>& v) {
-    if (v.empty()) return 0.0;
+template <typename T>
+static T median_of(std::vector<T>& v) {
+    if (v.empty()) return 0;
     std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
     return v[v.size() / 2];
 }
@@ -1197,13 +1183,12 @@ static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long
     census.bad_units(res->first_bad_unit, res->bad_list, &res->listed);
     if (res->bad_waves == 0) return NA_OK;
     const uint32_t* u = res->first_bad_unit;
-    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "%s: %llu of %llu waves wrong on %llu CU(s), first wave %llu on "
-                  "xcc%u.se%u.sh%u.cu%u.simd%u",
-                  fam.label, (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
-                  (unsigned long long)res->bad_units, (unsigned long long)res->first_bad_wave,
-                  u[0], u[1], u[2], u[3], u[4]);
-    return NA_ERR_VERIFY;
+    return na_error(NA_ERR_VERIFY,
+                    "%s: %llu of %llu waves wrong on %llu CU(s), first wave %llu on "
+                    "xcc%u.se%u.sh%u.cu%u.simd%u",
+                    fam.label, (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, (unsigned long long)res->first_bad_wave,
+                    u[0], u[1], u[2], u[3], u[4]);
 }
 
 // Whole sweep: one untimed warm-up launch, the timed launch, the verify.
@@ -1549,15 +1534,14 @@ extern "C" int na_lds_sweep_verify(const na_lds_record* recs, long long n, long 
                       (unsigned long long)res->first_bad_offset,
                       (unsigned long long)(res->first_bad_offset / 4 % 64),
                       (unsigned long long)res->xor_mask);
-    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "lds sweep: %llu of %llu workgroups wrong on %llu CU(s), first workgroup %llu "
-                  "in phase %s on xcc%u.se%u.sh%u.cu%u%s",
-                  (unsigned long long)res->bad_workgroups, (unsigned long long)res->workgroups,
-                  (unsigned long long)res->bad_units,
-                  (unsigned long long)res->first_bad_workgroup,
-                  res->first_bad_phase < LS_PHASES ? ls_phase_names[res->first_bad_phase] : "index",
-                  u[0], u[1], u[2], u[3], where);
-    return NA_ERR_VERIFY;
+    return na_error(
+        NA_ERR_VERIFY,
+        "lds sweep: %llu of %llu workgroups wrong on %llu CU(s), first workgroup %llu in phase %s "
+        "on xcc%u.se%u.sh%u.cu%u%s",
+        (unsigned long long)res->bad_workgroups, (unsigned long long)res->workgroups,
+        (unsigned long long)res->bad_units, (unsigned long long)res->first_bad_workgroup,
+        res->first_bad_phase < LS_PHASES ? ls_phase_names[res->first_bad_phase] : "index", u[0],
+        u[1], u[2], u[3], where);
 }
 
 // Whole sweep: one untimed warm-up launch, the timed launch, the verify.
@@ -1852,13 +1836,14 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
 
     std::vector<uint32_t> mask((size_t)n, 0);
     sweep_census census;
-    std::vector<double> rate, cycles;
+    std::vector<double> rate;
+    std::vector<uint64_t> cycles;
     for (long long i = 0; i < n; ++i) {
         const na_valu_record& r = recs[i];
         census.see(r, r.simd);
         if (r.cycles) {
             rate.push_back((double)iters * VS_FLOP_PER_ITER / (double)r.cycles);
-            cycles.push_back((double)r.cycles);
+            cycles.push_back(r.cycles);
         }
         uint64_t want[VS_PHASES];
         vs_expected(base, (uint64_t)i, iters, want);
@@ -1899,7 +1884,7 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
     res->clock_mhz = census.clock_mhz();
     if (!rate.empty()) res->min_flop_per_clk = *std::min_element(rate.begin(), rate.end());
     res->median_flop_per_clk = median_of(rate);
-    res->median_cycles = (uint64_t)median_of(cycles);
+    res->median_cycles = median_of(cycles);
     res->tflops = res->median_flop_per_clk * (double)res->simds_seen * res->clock_mhz / 1e6;
     if (res->bad_waves == 0) return NA_OK;
     const uint32_t* u = res->bad_list[0];
@@ -1916,12 +1901,11 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
                       slot < 256 ? 'a' : 'v', slot < 256 ? slot : slot - 256 + VS_FIRST_VGPR,
                       res->rf_first_lane, res->rf_xor);
     }
-    std::snprintf(na_last_error_buf, sizeof(na_last_error_buf),
-                  "valu sweep: %llu of %llu waves wrong, first wave %u in phase %s on "
-                  "xcc%u.se%u.sh%u.cu%u.simd%u%s",
-                  (unsigned long long)res->bad_waves, (unsigned long long)res->waves, u[0], phases,
-                  u[1], u[2], u[3], u[4], u[5], where);
-    return NA_ERR_VERIFY;
+    return na_error(NA_ERR_VERIFY,
+                    "valu sweep: %llu of %llu waves wrong, first wave %u in phase %s on "
+                    "xcc%u.se%u.sh%u.cu%u.simd%u%s",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves, u[0],
+                    phases, u[1], u[2], u[3], u[4], u[5], where);
 }
 
 // Whole sweep: one untimed warm-up launch, the timed launch, the verify.

@@ -493,6 +493,18 @@ def test_verify_duplicated_and_missing_wave(cpu_agent):
     assert "index" in dict((b[0], b[2]) for b in res.bad)[7]
 
 
+def test_verify_unwritten_records_median_cycles_is_the_integer_itself(cpu_agent):
+    """Eight records no wave wrote: every cycle count is 2^64 - 1, which a
+    median taken through double would round to 2^64 and convert back out of
+    range."""
+    recs = (nodeagent.ValuRecord * 8)()
+    ctypes.memset(recs, 0xFF, ctypes.sizeof(recs))
+    rc, res = cpu_agent.valu_sweep_verify(recs, ITERS)
+    assert rc == nodeagent.NA_ERR_VERIFY
+    assert res.median_cycles == 2**64 - 1
+    assert res.bad_waves == 8
+
+
 def test_verify_workgroup_not_on_four_simds_of_one_cu(cpu_agent):
     recs = _records(12)
     recs[6].simd = recs[5].simd  # two waves of workgroup 1 on one SIMD
