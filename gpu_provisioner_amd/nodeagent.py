@@ -36,7 +36,7 @@ MIN_XGMI_BW_GBS = 30.0
 # measured ~4.9 TB/s on healthy silicon (profiles/), floor leaves margin
 MIN_SDMA_BW_GBS = 3000.0
 
-# C ABI return codes (nodeagent/agent.hip)
+# C ABI return codes (nodeagent/nodeagent.h: NA_OK .. NA_ERR_ARG)
 NA_OK = 0
 NA_ERR_HIP = -1
 NA_ERR_VERIFY = -2
@@ -54,8 +54,9 @@ MEMTEST_FREE_FRACTION_PCT = 90
 # are those of nodeagent/mfmasweep.h.
 DEFAULT_MFMA_SWEEP_SEED = 0x4D493335_35584D53
 MFMA_SWEEP_DTYPES = {"bf16": 0, "fp8": 1}
-MFMA_SWEEP_WAVES_PER_WG = 4
-MFMA_SWEEP_MAX_LISTED = 8
+MFMA_SWEEP_WAVES_PER_WG = 4  # nodeagent/nodeagent.h: NA_SWEEP_WAVES_PER_WG
+# nodeagent/nodeagent.h: NA_SWEEP_MAX_LISTED, the one limit of all three sweeps' lists
+MFMA_SWEEP_MAX_LISTED = LDS_SWEEP_MAX_LISTED = VALU_SWEEP_MAX_LISTED = 8
 NO_BAD_WAVE = (1 << 64) - 1
 # bf16 floor of the default sweep: 0.70 x the 2282.1 TFLOP/s median measured
 # on MI355X (profiles/mfma_sweep_mi355x.txt); the margin covers the 12 %
@@ -98,9 +99,9 @@ MIN_MX_SWEEP_TFLOPS = 5370.5
 # a record carries one checksum per phase, in this order.
 DEFAULT_LDS_SWEEP_SEED = 0x4D493335_35584C53
 LDS_SWEEP_PHASES = ("b32", "b128", "dma16", "dma4", "dma12", "tr16", "atomic", "stream")
+# nodeagent/nodeagent.h: NA_LDS_PHASES of them, NA_LDS_GRANULE, NA_LDS_MAX_BYTES
 LDS_SWEEP_GRANULE = 4096  # lds_bytes is a multiple of this
 LDS_SWEEP_MAX_BYTES = 160 * 1024
-LDS_SWEEP_MAX_LISTED = 8
 LDS_SWEEP_PEAK_BYTES_PER_CLK = 256  # what a CU's LDS delivers per clock: a ceiling, no floor
 NO_BAD_WORKGROUP = (1 << 64) - 1
 # Floor of the default sweep's chip-wide stream rate: 0.70 x the 117806.3 GB/s
@@ -118,8 +119,8 @@ DEFAULT_VALU_SWEEP_SEED = 0x4D493335_35585653
 VALU_SWEEP_PHASES = ("rf", "rf_inv", "i32", "f32", "f64", "pk", "xlane", "trans", "stream")
 VALU_SWEEP_MASK_NAMES = VALU_SWEEP_PHASES + ("index", "placement")
 VALU_SWEEP_FIRST_VGPR = 32  # v0..v31 hold the test's own state and are not pattern-tested
+# nodeagent/nodeagent.h: NA_VALU_MAX_ITERS (and NA_VALU_PHASES phases above)
 VALU_SWEEP_MAX_ITERS = ((1 << 24) - 2048) // 2 - 1  # the stream phase is exact up to here
-VALU_SWEEP_MAX_LISTED = 8
 VALU_SWEEP_XLANE_MOVES = 8
 NO_BAD_SLOT = (1 << 32) - 1
 # FLOP per clock of one SIMD at the vector f32 peak (157.3 TFLOP/s over 1024
@@ -492,10 +493,88 @@ class ValuSweepResult:
         })
 
 
+# The binding of nodeagent/nodeagent.h: one row per prototype, in its order,
+# as symbol -> (restype, argtypes) with the types spelled as the prototype
+# spells them. _load_lib applies it, so a plain Python int reaches a 64-bit
+# or pointer parameter whole. tests/test_nodeagent_abi.py holds the table and
+# the Structure classes above against the header.
+_int, _i64, _u64, _void_p = ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_void_p
+_P = ctypes.POINTER
+_int_p, _i64_p, _u64_p, _double_p = _P(_int), _P(_i64), _P(ctypes.c_uint64), _P(ctypes.c_double)
+_char_p = _P(ctypes.c_char)  # a buffer the callee fills
+_DEV = (_int, (_int,))  # int fn(int dev)
+_BANDWIDTH = (_int, (_int, _i64, _int, _double_p))
+_CHECK_RUN = (_int, (_int, _int, _void_p, _int))
+_CHECK_VERIFY = (_int, (_int, _void_p, _int))
+_WAVE_EXPECTED = (_int, (_u64, _u64, _int, _u64_p))
+_MATRIX_RUN = (_int, (_int, _int, _int, _int, _u64, _P(MfmaRecord), _i64, _double_p))
+_MATRIX_VERIFY = (_int, (_P(MfmaRecord), _i64, _int, _u64, _P(_MfmaSweepResultC)))
+_MATRIX_SWEEP = (_int, (_int, _int, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p))
+_ABI = {
+    "na_last_error": (ctypes.c_char_p, ()),
+    "na_device_count": (_int, (_int_p,)),
+    "na_device_info": (_int, (_int, _char_p, _int, _char_p, _int, _i64_p, _int_p, _int_p)),
+    "na_hbm_bandwidth": _BANDWIDTH,
+    "na_fma_selftest": _DEV,
+    "na_mfma_check_run": _CHECK_RUN,
+    "na_mfma_check_verify": _CHECK_VERIFY,
+    "na_mfma_selftest": _DEV,
+    "na_mfma_bf16_selftest": _DEV,
+    "na_mfma_fp8_selftest": _DEV,
+    "na_mfma_bf16_tile_check": _DEV,
+    "na_mfma_f16_tile_check": _DEV,
+    "na_mfma_fp8_tile_check": _DEV,
+    "na_mfma_i8_tile_check": _DEV,
+    "na_mfma_bf16_tile32_check": _DEV,
+    "na_mfma_mx_tile_check": _DEV,
+    "na_mx_decode": (_int, (_int, _int, _P(ctypes.c_float))),
+    "na_mx_pack": (_int, (_int, _int_p, _int, _P(ctypes.c_uint32), _int)),
+    "na_mx_check_run": _CHECK_RUN,
+    "na_mx_check_verify": _CHECK_VERIFY,
+    "na_mx_checks": _DEV,
+    "na_lds_selftest": (_int, (_int, _i64_p)),
+    "na_sdma_bandwidth": _BANDWIDTH,
+    "na_p2p_matrix": (_int, (_int, _int_p)),
+    "na_p2p_bandwidth": (_int, (_int, _int, _i64, _int, _double_p)),
+    "na_mem_info": (_int, (_int, _i64_p, _i64_p)),
+    "na_memtest_fill": (_int, (_int, _void_p, _i64, _u64, _int)),
+    "na_memtest_verify": (_int, (_int, _void_p, _i64, _u64, _int, _int, _P(_MemtestResultC))),
+    "na_hbm_memtest_passes": (
+        _int, (_int, _i64, _int, _u64, _P(_MemtestResultC), _double_p, _double_p)),
+    "na_hbm_memtest": (_int, (_int, _i64, _int, _u64, _P(_MemtestResultC), _double_p)),
+    "na_mfma_sweep_expected": _WAVE_EXPECTED,
+    "na_mfma_sweep_run": _MATRIX_RUN,
+    "na_mfma_sweep_verify": _MATRIX_VERIFY,
+    "na_mfma_sweep": _MATRIX_SWEEP,
+    "na_mx_sweep_expected": _WAVE_EXPECTED,
+    "na_mx_sweep_run": _MATRIX_RUN,
+    "na_mx_sweep_verify": _MATRIX_VERIFY,
+    "na_mx_sweep": _MATRIX_SWEEP,
+    "na_lds_sweep_allocation": (_int, (_int, _i64_p)),
+    "na_lds_sweep_expected": (_int, (_u64, _u64, _i64, _int, _u64_p, _int)),
+    "na_lds_sweep_run": (_int, (_int, _int, _i64, _int, _u64, _P(LdsRecord), _i64, _double_p)),
+    "na_lds_sweep_verify": (_int, (_P(LdsRecord), _i64, _i64, _int, _u64, _P(_LdsSweepResultC))),
+    "na_lds_sweep": (_int, (_int, _int, _i64, _int, _u64, _P(_LdsSweepResultC), _double_p)),
+    "na_valu_sweep_xlane_table": (_int, (_int, _int_p, _int)),
+    "na_valu_sweep_slots": (_int, ()),
+    "na_valu_sweep_expected": _WAVE_EXPECTED,
+    "na_valu_sweep_run": (_int, (_int, _int, _int, _u64, _P(ValuRecord), _i64, _double_p)),
+    "na_valu_sweep_verify": (_int, (_P(ValuRecord), _i64, _int, _u64, _P(_ValuSweepResultC))),
+    "na_valu_sweep": (_int, (_int, _int, _int, _u64, _P(_ValuSweepResultC))),
+}
+
+
 def _load_lib() -> ctypes.CDLL:
     for p in _SEARCH_PATHS:
         if os.path.exists(p):
-            return ctypes.CDLL(os.path.abspath(p))
+            lib = ctypes.CDLL(os.path.abspath(p))
+            for symbol, (restype, argtypes) in _ABI.items():
+                try:
+                    fn = getattr(lib, symbol)
+                except AttributeError:
+                    raise NodeAgentError(f"{p} does not export {symbol}; rebuild it") from None
+                fn.restype, fn.argtypes = restype, argtypes
+            return lib
     raise NodeAgentError(
         f"{_LIB_NAME} not found (searched {', '.join(_SEARCH_PATHS)}); "
         "build it with __graft_entry__.build() / make -C nodeagent"
@@ -562,7 +641,6 @@ class NodeReport:
 class NodeAgent:
     def __init__(self):
         self.lib = _load_lib()
-        self.lib.na_last_error.restype = ctypes.c_char_p
 
     def _err(self) -> str:
         return (self.lib.na_last_error() or b"").decode()
@@ -592,9 +670,7 @@ class NodeAgent:
 
     def hbm_bandwidth(self, dev: int, bytes_: int = 1 << 30, iters: int = 10) -> float:
         out = ctypes.c_double(0)
-        rc = self.lib.na_hbm_bandwidth(
-            dev, ctypes.c_longlong(bytes_), iters, ctypes.byref(out)
-        )
+        rc = self.lib.na_hbm_bandwidth(dev, bytes_, iters, ctypes.byref(out))
         self._check(rc, f"hbm_bandwidth({dev})")
         return out.value
 
@@ -721,7 +797,7 @@ class NodeAgent:
     def sdma_bandwidth(self, dev: int, bytes_: int = 512 << 20, iters: int = 10) -> float:
         """D2D copy through the SDMA engines — RCCL's xGMI transport hardware."""
         out = ctypes.c_double(0)
-        rc = self.lib.na_sdma_bandwidth(dev, ctypes.c_longlong(bytes_), iters, ctypes.byref(out))
+        rc = self.lib.na_sdma_bandwidth(dev, bytes_, iters, ctypes.byref(out))
         self._check(rc, f"sdma_bandwidth({dev})")
         return out.value
 
@@ -740,10 +816,7 @@ class NodeAgent:
         """Write the test pattern to caller-owned device memory (``ptr``
         16-byte aligned, ``bytes_`` a positive multiple of 16). Returns the
         C return code (``NA_ERR_ARG`` for a bad pointer/size)."""
-        return self.lib.na_memtest_fill(
-            dev, ctypes.c_void_p(ptr), ctypes.c_longlong(bytes_),
-            ctypes.c_ulonglong(seed), int(bool(invert)),
-        )
+        return self.lib.na_memtest_fill(dev, ptr, bytes_, seed, int(bool(invert)))
 
     def memtest_verify(self, dev: int, ptr: int, bytes_: int,
                        seed: int = DEFAULT_MEMTEST_SEED, invert: bool = False,
@@ -753,8 +826,7 @@ class NodeAgent:
         ``(rc, MemtestResult)``; rc is ``NA_ERR_VERIFY`` on any mismatch."""
         res = _MemtestResultC()
         rc = self.lib.na_memtest_verify(
-            dev, ctypes.c_void_p(ptr), ctypes.c_longlong(bytes_),
-            ctypes.c_ulonglong(seed), int(bool(invert)), int(bool(flip)), ctypes.byref(res),
+            dev, ptr, bytes_, seed, int(bool(invert)), int(bool(flip)), ctypes.byref(res),
         )
         if rc not in (NA_OK, NA_ERR_VERIFY):
             return rc, MemtestResult()
@@ -775,8 +847,7 @@ class NodeAgent:
         res = _MemtestResultC()
         gbs = ctypes.c_double(0)
         rc = self.lib.na_hbm_memtest(
-            dev, ctypes.c_longlong(bytes_), rounds, ctypes.c_ulonglong(seed),
-            ctypes.byref(res), ctypes.byref(gbs),
+            dev, bytes_, rounds, seed, ctypes.byref(res), ctypes.byref(gbs)
         )
         if rc not in (NA_OK, NA_ERR_VERIFY):
             err = self._err()
@@ -805,6 +876,12 @@ class NodeAgent:
             g.problems.append(f"HBM memtest: {res.describe()}")
 
     # -- what the chip-wide sweeps' wrappers share ------------------------------
+    #
+    # The whole-sweep entry points (na_*_sweep) are the ones check() reaches,
+    # so the tests' stand-in libraries define them, and those read the seed
+    # and lds_bytes through ``.value``. _matrix_sweep, lds_sweep and valu_sweep
+    # therefore still hand them over in their C types; the binding accepts
+    # either form. Every other call passes plain ints.
 
     def _sweep_run(self, what, record_type, n, *args) -> tuple:
         """``na_<what>`` with ``args`` ahead of the ``n`` records it fills.
@@ -812,7 +889,7 @@ class NodeAgent:
         recs = (record_type * max(n, 1))()
         ms = ctypes.c_double(0)
         dev = args[0]
-        rc = getattr(self.lib, f"na_{what}")(*args, recs, ctypes.c_longlong(n), ctypes.byref(ms))
+        rc = getattr(self.lib, f"na_{what}")(*args, recs, n, ctypes.byref(ms))
         self._check(rc, f"{what}({dev})")
         return recs, ms.value
 
@@ -820,9 +897,7 @@ class NodeAgent:
         """``na_<what>`` on ``recs`` with ``args`` between the record count and
         the C result ``res``. Returns ``(rc, wrap(res))``, or ``(rc, empty())``
         when the call itself was refused."""
-        rc = getattr(self.lib, f"na_{what}")(
-            recs, ctypes.c_longlong(len(recs)), *args, ctypes.byref(res)
-        )
+        rc = getattr(self.lib, f"na_{what}")(recs, len(recs), *args, ctypes.byref(res))
         return rc, wrap(res) if rc in (NA_OK, NA_ERR_VERIFY) else empty()
 
     # The matrix-core sweep's two families, "mfma" (dtypes) and "mx" (formats),
@@ -838,21 +913,19 @@ class NodeAgent:
 
     def _matrix_sweep_expected(self, fam, wave, outer, seed) -> int:
         out = ctypes.c_uint64(0)
-        rc = getattr(self.lib, f"na_{fam}_sweep_expected")(
-            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), outer, ctypes.byref(out)
-        )
+        rc = getattr(self.lib, f"na_{fam}_sweep_expected")(seed, wave, outer, ctypes.byref(out))
         self._check(rc, f"{fam}_sweep_expected")
         return out.value
 
     def _matrix_sweep_run(self, fam, dev, name, workgroups, outer, seed) -> tuple:
         return self._sweep_run(
             f"{fam}_sweep_run", MfmaRecord, max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG,
-            dev, self._matrix_code(fam, name), workgroups, outer, ctypes.c_ulonglong(seed),
+            dev, self._matrix_code(fam, name), workgroups, outer, seed,
         )
 
     def _matrix_sweep_verify(self, fam, recs, outer, seed, name) -> tuple:
         return self._sweep_verify(
-            f"{fam}_sweep_verify", recs, (outer, ctypes.c_ulonglong(seed)), _MfmaSweepResultC(),
+            f"{fam}_sweep_verify", recs, (outer, seed), _MfmaSweepResultC(),
             lambda res: MfmaSweepResult._from_c(name, res), lambda: MfmaSweepResult(name),
         )
 
@@ -974,10 +1047,7 @@ class NodeAgent:
         of 4096 up to 160 KiB) with ``iters`` stream passes (host arithmetic
         only; needs no GPU)."""
         out = (ctypes.c_uint64 * len(LDS_SWEEP_PHASES))()
-        rc = self.lib.na_lds_sweep_expected(
-            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(workgroup), ctypes.c_longlong(lds_bytes),
-            iters, out, len(out),
-        )
+        rc = self.lib.na_lds_sweep_expected(seed, workgroup, lds_bytes, iters, out, len(out))
         self._check(rc, "lds_sweep_expected")
         return list(out)
 
@@ -989,7 +1059,7 @@ class NodeAgent:
         ``LdsRecord`` (record i is workgroup i) and the HIP-event time."""
         return self._sweep_run(
             "lds_sweep_run", LdsRecord, max(workgroups, 0),
-            dev, workgroups, ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed),
+            dev, workgroups, lds_bytes, iters, seed,
         )
 
     def lds_sweep_verify(self, recs, lds_bytes: int, iters: int,
@@ -999,9 +1069,8 @@ class NodeAgent:
         LdsSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad workgroup, and
         ``na_last_error`` then names the first failing phase and CU."""
         return self._sweep_verify(
-            "lds_sweep_verify", recs,
-            (ctypes.c_longlong(lds_bytes), iters, ctypes.c_ulonglong(seed)),
-            _LdsSweepResultC(), LdsSweepResult._from_c, LdsSweepResult,
+            "lds_sweep_verify", recs, (lds_bytes, iters, seed), _LdsSweepResultC(),
+            LdsSweepResult._from_c, LdsSweepResult,
         )
 
     def lds_sweep(self, dev: int, workgroups: int = 0, lds_bytes: int = 0, iters: int = 0,
@@ -1059,9 +1128,7 @@ class NodeAgent:
         entry, which has no host reference, is 0 (host arithmetic only; needs
         no GPU)."""
         out = (ctypes.c_uint64 * len(VALU_SWEEP_PHASES))()
-        rc = self.lib.na_valu_sweep_expected(
-            ctypes.c_ulonglong(seed), ctypes.c_ulonglong(wave), iters, out
-        )
+        rc = self.lib.na_valu_sweep_expected(seed, wave, iters, out)
         self._check(rc, "valu_sweep_expected")
         return list(out)
 
@@ -1072,7 +1139,7 @@ class NodeAgent:
         array of ``ValuRecord`` (record i is wave i) and the HIP-event time."""
         return self._sweep_run(
             "valu_sweep_run", ValuRecord, max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG,
-            dev, workgroups, iters, ctypes.c_ulonglong(seed),
+            dev, workgroups, iters, seed,
         )
 
     def valu_sweep_verify(self, recs, iters: int, seed: int = DEFAULT_VALU_SWEEP_SEED) -> tuple:
@@ -1081,7 +1148,7 @@ class NodeAgent:
         ValuSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad wave, and
         ``na_last_error`` then names the first failing unit and phase."""
         return self._sweep_verify(
-            "valu_sweep_verify", recs, (iters, ctypes.c_ulonglong(seed)),
+            "valu_sweep_verify", recs, (iters, seed),
             _ValuSweepResultC(), ValuSweepResult._from_c, ValuSweepResult,
         )
 
@@ -1124,9 +1191,7 @@ class NodeAgent:
 
     def p2p_bandwidth(self, src: int, dst: int, bytes_: int = 256 << 20, iters: int = 5) -> float:
         out = ctypes.c_double(0)
-        rc = self.lib.na_p2p_bandwidth(
-            src, dst, ctypes.c_longlong(bytes_), iters, ctypes.byref(out)
-        )
+        rc = self.lib.na_p2p_bandwidth(src, dst, bytes_, iters, ctypes.byref(out))
         self._check(rc, f"p2p_bandwidth({src},{dst})")
         return out.value
 

@@ -23,8 +23,9 @@
 // sweeps" below): a further sweep starts from those.
 //
 // Built for gfx950 only (hipcc --offload-arch=gfx950); exposed as a C ABI
-// consumed by gpu_provisioner_amd/nodeagent.py (ctypes) both as a CLI and in
-// the k8s DaemonSet health probe.
+// (nodeagent.h: return codes, limits, record and result structs, one
+// prototype per entry point) consumed by gpu_provisioner_amd/nodeagent.py
+// (ctypes) both as a CLI and in the k8s DaemonSet health probe.
 
 #include <hip/hip_runtime.h>
 
@@ -39,12 +40,8 @@
 
 #include "memtest.h"
 #include "mfma_frag.h"
+#include "nodeagent.h"
 #include "sweep_common.h"
-
-#define NA_OK 0
-#define NA_ERR_HIP -1
-#define NA_ERR_VERIFY -2
-#define NA_ERR_ARG -3
 
 static char na_last_error_buf[512];
 
@@ -728,10 +725,6 @@ extern "C" int na_p2p_bandwidth(int src, int dst, long long bytes, int iters, do
 // here is what ECC does not fix — uncorrected/multi-bit corruption,
 // addressing faults and data-path faults.
 
-typedef struct {
-    uint64_t bytes_tested, bad_words, first_bad_offset /* UINT64_MAX = none */, xor_mask;
-} na_memtest_result;
-
 extern "C" int na_mem_info(int dev, long long* free_bytes, long long* total_bytes) {
     HIP_CHECK(hipSetDevice(dev));
     size_t free_b = 0, total_b = 0;
@@ -929,8 +922,6 @@ extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned lon
 // LDS size they launch with (sweep_lds_bytes) is further up, with
 // na_lds_selftest, which tests the same allocation.
 
-#define SWEEP_MAX_LISTED 8
-
 // What 0 means to the whole-sweep entry points: four workgroups per CU, and
 // the sweep's default count of folds, passes or rounds.
 static int sweep_defaults(int dev, int* workgroups, int* iters, int default_iters) {
@@ -989,7 +980,7 @@ struct sweep_census {
     std::vector<double> mhz;  // cycles / realtime x 100 MHz, per record
     uint64_t cus_seen = 0, simds_seen = 0, bad_cus = 0;
     uint32_t first_bad[5] = {}, listed = 0;  // the first bad unit; 0s for none
-    uint32_t bad_list[SWEEP_MAX_LISTED][5] = {};  // the first distinct bad units
+    uint32_t bad_list[NA_SWEEP_MAX_LISTED][5] = {};  // the first distinct bad units
 
     sweep_census() : cu_seen(1 << 11), simd_seen(1 << 13), cu_bad(1 << 11) {}
 
@@ -1009,14 +1000,14 @@ struct sweep_census {
         bool known = false;
         for (uint32_t k = 0; k < listed && !known; ++k)
             known = std::memcmp(bad_list[k], unit, sizeof(unit)) == 0;
-        if (!known && listed < SWEEP_MAX_LISTED)
+        if (!known && listed < NA_SWEEP_MAX_LISTED)
             std::memcpy(bad_list[listed++], unit, sizeof(unit));
     }
 
     // The leading W fields of the first bad unit and of the listed ones, into
     // a result struct's arrays.
     template <int W>
-    void bad_units(uint32_t (&first)[W], uint32_t (&list)[SWEEP_MAX_LISTED][W],
+    void bad_units(uint32_t (&first)[W], uint32_t (&list)[NA_SWEEP_MAX_LISTED][W],
                    uint32_t* n) const {
         *n = listed;
         std::memcpy(first, first_bad, sizeof(first));
@@ -1040,7 +1031,6 @@ struct sweep_census {
 
 #include "mfmasweep.h"
 
-#define NA_MFMA_MAX_LISTED 8
 #define NA_MFMA_MAX_WORKGROUPS (1 << 20)
 #define NA_MFMA_MAX_OUTER (1 << 22)  // ~2 s per resident wave: keeps a typo from hanging the node
 // 8192 folds x 64 MFMAs x 16 cycles is ~3.5 ms per workgroup at 2.4 GHz, and
@@ -1049,16 +1039,6 @@ struct sweep_census {
 // (profiles/mfma_sweep_mi355x.txt) — past the 10 ms from which the
 // in-kernel clock estimate is reliable.
 #define NA_MFMA_DEFAULT_OUTER 8192
-
-typedef struct {
-    uint64_t waves, bad_waves;
-    uint64_t units_seen, bad_units;  // distinct (xcc, se, sh, cu)
-    uint64_t first_bad_wave;         // UINT64_MAX = none
-    double clock_mhz;                // median of cycles / realtime x 100 MHz
-    uint32_t first_bad_unit[5];      // xcc, se, sh, cu, simd
-    uint32_t listed;                 // entries used in bad_list
-    uint32_t bad_list[NA_MFMA_MAX_LISTED][5];  // first distinct failing (xcc, se, sh, cu, simd)
-} na_mfma_sweep_result;
 
 // S(n) = sum_{j<n} q^j mod 2^64 by binary expansion of n.
 static uint64_t ms_geometric_sum(uint64_t q, uint64_t n) {
@@ -1267,7 +1247,6 @@ extern "C" int na_mx_sweep(int dev, int format, int workgroups, int outer,
 
 #include "ldssweep.h"
 
-#define NA_LDS_MAX_LISTED 8
 #define NA_LDS_MAX_WORKGROUPS (1 << 20)
 // A pass over 160 KiB is 640 clocks at the LDS's 256 B/clk, 0.27 us at
 // 2.4 GHz: 2^22 passes hold a CU for ~1.1 s at full rate, ~2 s at the half
@@ -1284,23 +1263,6 @@ extern "C" int na_mx_sweep(int dev, int format, int workgroups, int outer,
 
 static const char* const ls_phase_names[LS_PHASES] = {"b32",   "b128", "dma16",  "dma4",
                                                       "dma12", "tr16", "atomic", "stream"};
-
-typedef struct {
-    uint64_t workgroups, bad_workgroups;
-    uint64_t units_seen, bad_units;   // distinct (xcc, se, sh, cu)
-    uint64_t first_bad_workgroup;     // UINT64_MAX = none
-    // of the first bad workgroup, when its first failing phase compares words
-    // in the kernel; otherwise 0, UINT64_MAX, 0
-    uint64_t bad_words, first_bad_offset, xor_mask;
-    double clock_mhz;                 // median of cycles / realtime x 100 MHz
-    // stream phase, iters * lds_bytes / cycles per workgroup: bytes per
-    // shader clock of the CU it ran on
-    double median_bytes_per_clk, min_bytes_per_clk, max_bytes_per_clk;
-    uint32_t first_bad_unit[4];       // xcc, se, sh, cu
-    uint32_t first_bad_phase;         // LS_* code; LS_PHASES = the record's index
-    uint32_t listed;                  // entries used in bad_list
-    uint32_t bad_list[NA_LDS_MAX_LISTED][4];  // first distinct failing (xcc, se, sh, cu)
-} na_lds_sweep_result;
 
 // Per 1 KiB chunk of each pattern, the sums the checksums are linear in.
 // They do not depend on the workgroup, whose rotation only selects which
@@ -1590,7 +1552,6 @@ extern "C" int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int it
 
 #include "valusweep.h"
 
-#define NA_VALU_MAX_LISTED 8
 #define NA_VALU_MAX_WORKGROUPS (1 << 20)
 // Bits of a listed wave's phase mask above the VS_PHASES checksum bits: the
 // record does not carry its own index (a missing or duplicated wave), or the
@@ -1603,23 +1564,6 @@ extern "C" int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int it
 // (profiles/valu_sweep_mi355x.txt) — past the 10 ms from which the in-kernel
 // clock estimate is reliable (see NA_MFMA_DEFAULT_OUTER).
 #define NA_VALU_DEFAULT_ITERS 131072
-
-typedef struct {
-    uint64_t waves, bad_waves;
-    uint64_t cus_seen, simds_seen;  // distinct (xcc, se, sh, cu) and (.., simd)
-    uint64_t trans_unchecked;       // 1: fewer than 3 records or no strict majority
-    uint64_t trans_consensus;       // the majority's trans checksum; 0 when unchecked
-    uint64_t median_cycles;         // of the stream phase
-    double clock_mhz;               // median of cycles / realtime x 100 MHz
-    // stream phase, FLOP per shader clock of the SIMD the wave ran on
-    double median_flop_per_clk, min_flop_per_clk;
-    double tflops;  // median_flop_per_clk x simds_seen x clock_mhz / 1e6
-    // the first listed wave's in-kernel register-file diagnosis
-    uint32_t rf_bad, rf_first_slot, rf_first_lane, rf_xor;
-    uint32_t listed;  // entries used in bad_list
-    // first bad waves: wave, xcc, se, sh, cu, simd, mask of failed phases
-    uint32_t bad_list[NA_VALU_MAX_LISTED][7];
-} na_valu_sweep_result;
 
 static const char* const vs_phase_names[VS_PHASES + 2] = {
     "rf", "rf_inv", "i32", "f32", "f64", "pk", "xlane", "trans", "stream", "index", "placement"};
@@ -1874,7 +1818,7 @@ extern "C" int na_valu_sweep_verify(const na_valu_record* recs, long long n, int
             res->rf_first_lane = r.rf_first_lane;
             res->rf_xor = r.rf_xor;
         }
-        if (res->listed < NA_VALU_MAX_LISTED) {
+        if (res->listed < NA_SWEEP_MAX_LISTED) {
             const uint32_t row[7] = {(uint32_t)i, r.xcc, r.se, r.sh, r.cu, r.simd, mask[i]};
             std::memcpy(res->bad_list[res->listed++], row, sizeof(row));
         }

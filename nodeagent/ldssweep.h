@@ -91,6 +91,7 @@
 #include <cstdint>
 
 #include "memtest.h"
+#include "nodeagent.h"
 #include "sweep_common.h"
 
 #define LS_BLOCK MS_BLOCK    // four waves, as every sweep
@@ -102,16 +103,10 @@
 enum { LS_B32, LS_B128, LS_DMA16, LS_DMA4, LS_DMA12, LS_TR16, LS_ATOMIC, LS_STREAM, LS_PHASES };
 enum { LS_PAT_B32, LS_PAT_B128, LS_PAT_DMA, LS_PAT_TR16, LS_PAT_ATOMIC, LS_PAT_STREAM };
 
-// One per workgroup, written by one thread. cycles/realtime are the deltas
-// of s_memtime (shader clock) and s_memrealtime (100 MHz) around the stream
-// phase. bad_phase is an LS_* code, 0xFFFFFFFF when bad_words is 0, and
-// first_bad_offset is then UINT64_MAX.
-typedef struct {
-    uint64_t checksum[LS_PHASES];
-    uint64_t bad_words, first_bad_offset, xor_mask;
-    uint64_t cycles, realtime;
-    uint32_t workgroup, bad_phase, xcc, se, sh, cu;
-} na_lds_record;
+// The kernel leaves one na_lds_record (nodeagent.h) per workgroup.
+static_assert(LS_PHASES == NA_LDS_PHASES && LS_GRANULE == NA_LDS_GRANULE &&
+                  LS_MAX_BYTES == NA_LDS_MAX_BYTES,
+              "nodeagent.h tells callers otherwise");
 
 __device__ __host__ inline uint32_t ls_pat(mt_u64 base, int pat, uint32_t j) {
     return (uint32_t)(mt_mix64(base + ((mt_u64)pat << 32) + j) >> 32);

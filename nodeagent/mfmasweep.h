@@ -44,6 +44,7 @@
 
 #include "memtest.h"
 #include "mfma_frag.h"
+#include "nodeagent.h"
 #include "sweep_common.h"
 
 #define MS_FRAGS 8
@@ -55,12 +56,7 @@
 // format f (0 = fp4, 1 = fp6) is MS_FP4 + f.
 enum { MS_BF16 = 0, MS_FP8 = 1, MS_FP4 = 2, MS_FP6 = 3, MS_DTYPES };
 
-// One per wave, written by one lane. cycles/realtime are the deltas of
-// s_memtime (shader clock) and s_memrealtime (100 MHz) around the fold loop.
-typedef struct {
-    uint64_t checksum, cycles, realtime;
-    uint32_t wave, xcc, se, sh, cu, simd;
-} na_mfma_record;
+// The kernel leaves one na_mfma_record (nodeagent.h) per wave.
 
 // k_len: K of the MFMA, 32 or 128.
 __device__ __host__ inline int ms_value(mt_u64 base, mt_u64 w, int m, int t, int r, int k,

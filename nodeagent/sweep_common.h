@@ -11,9 +11,11 @@
 #include <cstdint>
 
 #include "memtest.h"
+#include "nodeagent.h"
 
 #define MS_BLOCK 256  // four waves: one per SIMD of the CU
 #define MS_WAVES_PER_WG (MS_BLOCK / 64)
+static_assert(MS_WAVES_PER_WG == NA_SWEEP_WAVES_PER_WG, "nodeagent.h tells callers otherwise");
 #define MS_G 0x9E3779B97F4A7C15ULL
 // The LDS of one gfx950 CU. A workgroup launched with more than half of it
 // has the CU, and each of its four waves a SIMD, to itself.

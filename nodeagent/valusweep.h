@@ -116,6 +116,7 @@
 #include <cstdint>
 
 #include "memtest.h"
+#include "nodeagent.h"
 #include "sweep_common.h"
 
 #define VS_BLOCK MS_BLOCK  // four waves: one per SIMD of the CU
@@ -137,20 +138,9 @@
 
 enum { VS_RF, VS_RF_INV, VS_I32, VS_F32, VS_F64, VS_PK, VS_XLANE, VS_TRANS, VS_STREAM, VS_PHASES };
 
-// One per wave, written by one lane. cycles/realtime are the deltas of
-// s_memtime (shader clock) and s_memrealtime (100 MHz) around the stream
-// phase. The rf_* fields are the kernel's own comparison in the two
-// register-file phases: rf_bad counts wrong (slot, lane) pairs of both,
-// rf_first_slot is the slot of the first (rf before rf_inv, then lowest
-// slot, then lowest lane) plus 512 when it was seen in rf_inv, rf_first_lane
-// its lane, rf_xor the OR of got ^ want. With rf_bad 0 the slot and lane are
-// 0xFFFFFFFF.
-typedef struct {
-    uint64_t checksum[VS_PHASES];
-    uint64_t cycles, realtime;
-    uint32_t wave, xcc, se, sh, cu, simd;
-    uint32_t rf_bad, rf_first_slot, rf_first_lane, rf_xor;
-} na_valu_record;
+// The kernel leaves one na_valu_record (nodeagent.h) per wave.
+static_assert(VS_PHASES == NA_VALU_PHASES && VS_MAX_ITERS == NA_VALU_MAX_ITERS,
+              "nodeagent.h tells callers otherwise");
 
 __device__ __host__ inline mt_u64 vs_h(mt_u64 base, int p, mt_u64 i) {
     return mt_mix64(base + ((mt_u64)p << 32) + i);
