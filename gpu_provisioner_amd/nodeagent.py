@@ -7,7 +7,7 @@ there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
-[--valu-sweep]``
+[--cache-sweep] [--valu-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -110,6 +110,27 @@ NO_BAD_WORKGROUP = (1 << 64) - 1
 # loops has not been measured; 0.70 is borrowed from the MFMA floor above.
 # 0 disables the floor.
 MIN_LDS_SWEEP_GBS = 82464.4
+
+# Chip-wide cache sweep (nodeagent/cachesweep.h). The default seed is
+# "MI355XCS"; the records are the LDS sweep's, with one checksum per phase in
+# this order: the first six in the records of the first launch, xread in those
+# of the second.
+DEFAULT_CACHE_SWEEP_SEED = 0x4D493335_35584353
+CACHE_SWEEP_PHASES = ("l1", "l2", "wt", "atomic", "scalar", "stream", "xread")
+# nodeagent/nodeagent.h: NA_CACHE_PHASES of them, NA_CACHE_GRANULE,
+# NA_CACHE_MAX_BYTES, NA_CACHE_TABLE_WORDS
+CACHE_SWEEP_GRANULE = 4096  # slice_bytes is a multiple of this
+CACHE_SWEEP_MAX_BYTES = 1 << 20
+CACHE_SWEEP_TABLE_WORDS = 4096  # the scalar phase's read-only table
+# the phases an XCD's L2 serves: failures of these on several CUs of one XCC
+# point at that L2
+CACHE_SWEEP_L2_PHASES = ("l2", "wt", "atomic", "stream", "xread")
+# Floor of the default sweep's chip-wide stream rate: 0.70 x the 13950.1 GB/s
+# median of five processes on MI355X (profiles/cache_sweep_mi355x.txt; 23
+# bytes per clock and CU), the rule of the floors above. One workgroup per CU
+# is latency-bound, so the figure is far under what the L2s deliver at full
+# occupancy: a health floor, no benchmark. 0 disables the floor.
+MIN_CACHE_SWEEP_GBS = 9765.1
 
 # Chip-wide vector-unit sweep (nodeagent/valusweep.h). The default seed is
 # "MI355XVS"; a record carries one checksum per phase, in this order. A listed
@@ -380,6 +401,41 @@ class LdsSweepResult:
         })
 
 
+@dataclass
+class CacheSweepResult(LdsSweepResult):
+    """Outcome of a cache sweep verify: the LDS sweep's shape.
+    ``first_bad_phase`` is one of ``CACHE_SWEEP_PHASES`` or "index",
+    ``first_bad_offset`` the byte offset within the workgroup's slice, and
+    the diagnosis triple is filled when that phase compares words in the
+    kernel (l1, l2, wt, atomic, xread). The rates are the stream phase's bytes
+    per shader clock and CU, read from the L2."""
+
+    def describe(self) -> str:
+        names = ", ".join(mfma_unit_name(u) for u in self.bad_cus)
+        more = ", ..." if len(self.bad_cus) == LDS_SWEEP_MAX_LISTED else ""
+        if (self.first_bad_phase in CACHE_SWEEP_L2_PHASES and len(self.bad_cus) >= 2
+                and len({u[0] for u in self.bad_cus}) == 1 and self.bad_units == len(self.bad_cus)):
+            names, more = f"all on xcc{self.bad_cus[0][0]}: suspect its L2", ""
+        where = ""
+        if self.first_bad_offset != NO_BAD_OFFSET:
+            where = (
+                f", {self.bad_words} bad words, first at slice offset {self.first_bad_offset:#x}, "
+                f"failing bits {self.xor_mask:#010x}"
+            )
+        return (
+            f"{self.bad_workgroups} of {self.workgroups} workgroups wrong on {self.bad_units} "
+            f"CU(s): {names}{more}; first in phase {self.first_bad_phase}{where}"
+        )
+
+    @classmethod
+    def _from_c(cls, res: "_LdsSweepResultC", gbs: float = 0.0):
+        out = super()._from_c(res, gbs)
+        if res.first_bad_workgroup != NO_BAD_WORKGROUP:
+            out.first_bad_phase = (CACHE_SWEEP_PHASES + ("index",))[
+                min(res.first_bad_phase, len(CACHE_SWEEP_PHASES))]
+        return out
+
+
 class ValuRecord(ctypes.Structure):
     """One wave of the vector-unit sweep (``na_valu_record``): a checksum per
     phase of ``VALU_SWEEP_PHASES``, the s_memtime / s_memrealtime deltas around
@@ -555,6 +611,11 @@ _ABI = {
     "na_lds_sweep_run": (_int, (_int, _int, _i64, _int, _u64, _P(LdsRecord), _i64, _double_p)),
     "na_lds_sweep_verify": (_int, (_P(LdsRecord), _i64, _i64, _int, _u64, _P(_LdsSweepResultC))),
     "na_lds_sweep": (_int, (_int, _int, _i64, _int, _u64, _P(_LdsSweepResultC), _double_p)),
+    "na_cache_sweep_expected": (_int, (_u64, _u64, _u64, _i64, _int, _u64_p, _int)),
+    "na_cache_sweep_run": (_int, (_int, _int, _i64, _int, _u64, _P(LdsRecord), _i64, _double_p)),
+    "na_cache_sweep_verify": (
+        _int, (_P(LdsRecord), _i64, _i64, _int, _u64, _P(_LdsSweepResultC))),
+    "na_cache_sweep": (_int, (_int, _int, _i64, _int, _u64, _P(_LdsSweepResultC), _double_p)),
     "na_valu_sweep_xlane_table": (_int, (_int, _int_p, _int)),
     "na_valu_sweep_slots": (_int, ()),
     "na_valu_sweep_expected": _WAVE_EXPECTED,
@@ -600,6 +661,11 @@ class GPUReport:
     lds_sweep_min_cu_bytes_per_clk: float = 0.0
     lds_sweep_units_seen: int = 0
     lds_sweep_bad_workgroups: int = 0
+    # chip-wide cache sweep (opt-in; all "not run" by default)
+    cache_sweep_gbs: float = 0.0
+    cache_sweep_min_cu_bytes_per_clk: float = 0.0
+    cache_sweep_units_seen: int = 0
+    cache_sweep_bad_workgroups: int = 0
     # chip-wide vector-unit sweep (opt-in; all "not run" by default)
     valu_sweep_tflops: float = 0.0
     valu_sweep_min_simd_flop_per_clk: float = 0.0
@@ -879,8 +945,8 @@ class NodeAgent:
     #
     # The whole-sweep entry points (na_*_sweep) are the ones check() reaches,
     # so the tests' stand-in libraries define them, and those read the seed
-    # and lds_bytes through ``.value``. _matrix_sweep, lds_sweep and valu_sweep
-    # therefore still hand them over in their C types; the binding accepts
+    # and lds_bytes through ``.value``. _matrix_sweep, lds_sweep, cache_sweep and
+    # valu_sweep therefore still hand them over in their C types; the binding accepts
     # either form. Every other call passes plain ints.
 
     def _sweep_run(self, what, record_type, n, *args) -> tuple:
@@ -1105,6 +1171,77 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"LDS sweep: {res.describe()}")
 
+    # -- chip-wide cache sweep ---------------------------------------------------
+
+    def cache_sweep_expected(self, workgroup: int, workgroups: int, slice_bytes: int, iters: int,
+                             seed: int = DEFAULT_CACHE_SWEEP_SEED) -> list:
+        """The checksums workgroup ``workgroup`` of ``workgroups`` must
+        report, one per phase of ``CACHE_SWEEP_PHASES``, on a slice of
+        ``slice_bytes`` (a multiple of 4096 up to 1 MiB) with ``iters`` stream
+        passes: all but the last in its record of the first launch, the last
+        in that of the second (host arithmetic only; needs no GPU)."""
+        out = (ctypes.c_uint64 * len(CACHE_SWEEP_PHASES))()
+        rc = self.lib.na_cache_sweep_expected(
+            seed, workgroup, workgroups, slice_bytes, iters, out, len(out))
+        self._check(rc, "cache_sweep_expected")
+        return list(out)
+
+    def cache_sweep_run(self, dev: int, workgroups: int = 1, slice_bytes: int = 65536,
+                        iters: int = 1, seed: int = DEFAULT_CACHE_SWEEP_SEED) -> tuple:
+        """Both launches of ``workgroups`` workgroups, each on a slice of
+        ``slice_bytes`` of device memory with ``iters`` stream passes. Returns
+        ``(records, ms)``: a ctypes array of 2 x ``workgroups`` ``LdsRecord``
+        (record i is workgroup i mod ``workgroups`` of launch i //
+        ``workgroups``) and the HIP-event time of the pair."""
+        return self._sweep_run(
+            "cache_sweep_run", LdsRecord, 2 * max(workgroups, 0),
+            dev, workgroups, slice_bytes, iters, seed,
+        )
+
+    def cache_sweep_verify(self, recs, slice_bytes: int, iters: int,
+                           seed: int = DEFAULT_CACHE_SWEEP_SEED) -> tuple:
+        """Compare the records of both launches against the host reference.
+        Returns ``(rc, CacheSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad
+        record, and ``na_last_error`` then names the first failing phase and
+        CU, for ``xread`` also the CU that wrote the slice."""
+        return self._sweep_verify(
+            "cache_sweep_verify", recs, (slice_bytes, iters, seed), _LdsSweepResultC(),
+            CacheSweepResult._from_c, CacheSweepResult,
+        )
+
+    def cache_sweep(self, dev: int, workgroups: int = 0, slice_bytes: int = 0, iters: int = 0,
+                    seed: int = DEFAULT_CACHE_SWEEP_SEED) -> CacheSweepResult:
+        """Run one workgroup at a time on every CU through what lies between
+        a CU and HBM — the vector L1, the XCD's L2, write-through and refill,
+        global atomics, the scalar data cache — and a timed read stream from
+        the L2, then read every slice back from another workgroup, normally on
+        another XCD (``workgroups`` 0 = 4 per CU, ``slice_bytes`` 0 = 64 KiB,
+        ``iters`` 0 = the default pass count). Every phase of every workgroup
+        is verified bit-exactly against the host reference. Wrong workgroups
+        come back in the result (``.ok`` False) with the CUs they ran on, not
+        as an exception."""
+        res = _LdsSweepResultC()
+        gbs = ctypes.c_double(0)
+        rc = self.lib.na_cache_sweep(
+            dev, workgroups, ctypes.c_longlong(slice_bytes), iters, ctypes.c_ulonglong(seed),
+            ctypes.byref(res), ctypes.byref(gbs),
+        )
+        self._check(rc, f"cache_sweep({dev})", (NA_OK, NA_ERR_VERIFY))
+        return CacheSweepResult._from_c(res, gbs.value)
+
+    def _run_cache_sweep(self, g: GPUReport) -> None:
+        res = self.cache_sweep(g.index)
+        g.cache_sweep_gbs = round(res.gbs, 1)
+        g.cache_sweep_min_cu_bytes_per_clk = round(res.min_bytes_per_clk, 2)
+        g.cache_sweep_units_seen = res.units_seen
+        g.cache_sweep_bad_workgroups = res.bad_workgroups
+        if res.gbs < MIN_CACHE_SWEEP_GBS:
+            g.problems.append(
+                f"cache sweep: {g.cache_sweep_gbs} GB/s below floor {MIN_CACHE_SWEEP_GBS}"
+            )
+        if not res.ok:
+            g.problems.append(f"cache sweep: {res.describe()}")
+
     # -- chip-wide vector-unit sweep ---------------------------------------------
 
     def valu_sweep_slots(self) -> int:
@@ -1200,7 +1337,7 @@ class NodeAgent:
     def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
               memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
               mx_sweep: bool = False, lds_sweep: bool = False,
-              valu_sweep: bool = False) -> NodeReport:
+              valu_sweep: bool = False, cache_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -1233,7 +1370,14 @@ class NodeAgent:
         phases that failed, as is a stream rate under
         ``MIN_VALU_SWEEP_TFLOPS``. ``valu_sweep_simds_seen`` below 4 x the CU
         count and ``valu_sweep_trans_unchecked`` are reported, not problems.
-        False (default) makes no new library call."""
+        False (default) makes no new library call.
+
+        ``cache_sweep`` additionally runs the chip-wide cache sweep on every
+        GPU: a wrong workgroup is a problem that names its CU and the phase
+        that failed (or the XCC whose L2 is suspect), as is a stream rate
+        under ``MIN_CACHE_SWEEP_GBS``. ``cache_sweep_units_seen`` below the CU
+        count is reported, not a problem. False (default) makes no new
+        library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -1275,6 +1419,8 @@ class NodeAgent:
                     self._run_mx_sweep(g)
                 if lds_sweep:
                     self._run_lds_sweep(g)
+                if cache_sweep:
+                    self._run_cache_sweep(g)
                 if valu_sweep:
                     self._run_valu_sweep(g)
             except NodeAgentError as e:
@@ -1403,6 +1549,16 @@ def main(argv=None) -> int:
         "XCC/SE/SH/CU; reports the read-stream rate chip-wide and of the slowest CU",
     )
     ap.add_argument(
+        "--cache-sweep",
+        action="store_true",
+        help="also run the chip-wide cache sweep on every GPU: one workgroup at a time on "
+        "every CU, each on a cache-resident slice of device memory, through the vector L1, the "
+        "XCD's L2, write-through and refill, global atomics and the scalar data cache, then "
+        "every slice read back from another XCD; every phase checked bit-exactly and a wrong "
+        "one attributed to its XCC/SE/SH/CU; reports the L2 read-stream rate chip-wide and of "
+        "the slowest CU",
+    )
+    ap.add_argument(
         "--valu-sweep",
         action="store_true",
         help="also run the chip-wide vector-unit sweep on every GPU: one wave per SIMD of "
@@ -1429,6 +1585,7 @@ def main(argv=None) -> int:
             mx_sweep=args.mx_sweep,
             lds_sweep=args.lds_sweep,
             valu_sweep=args.valu_sweep,
+            cache_sweep=args.cache_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

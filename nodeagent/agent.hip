@@ -16,8 +16,10 @@
 // families of single-wave checks are rows of one table type with one
 // argument check, run and verify: check_run / check_verify), an
 // opt-in chip-wide LDS sweep (every LDS access path on every CU, ldssweep.h),
+// an opt-in chip-wide cache sweep (L1, L2, write-through, global atomics,
+// scalar cache and the cross-XCD read path from every CU, cachesweep.h),
 // an opt-in chip-wide vector-unit sweep (register file and VALU of every
-// SIMD, valusweep.h), and the xGMI peer-to-peer link matrix. The three
+// SIMD, valusweep.h), and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
 // sweeps" below): a further sweep starts from those.
@@ -912,8 +914,9 @@ extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned lon
 // Shared host side of the chip-wide sweeps (device side: sweep_common.h)
 // ---------------------------------------------------------------------------
 //
-// Each sweep below (matrix cores, LDS, vector unit) is a kernel that leaves
-// one record per wave or workgroup, a *_run that launches it once, a pure-host
+// Each sweep below (matrix cores, LDS, caches, vector unit) is a kernel that leaves
+// one record per wave or workgroup, a *_run that launches it once (the cache
+// sweep: its two kernels, one after the other), a pure-host
 // *_verify that recomputes every record's checksums, and an entry point that
 // runs twice and verifies. A sweep owns its reference, its verdict rules, its
 // messages and its argument checks; the launch (sweep_launch), the defaults
@@ -1533,6 +1536,324 @@ extern "C" int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int it
     });
     if (rc != NA_OK) return rc;
     rc = na_lds_sweep_verify(recs.data(), (long long)recs.size(), lds_bytes, iters, seed, res);
+    if (gbs && (rc == NA_OK || rc == NA_ERR_VERIFY))
+        *gbs = res->median_bytes_per_clk * (double)res->units_seen * res->clock_mhz / 1000.0;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide cache sweep (kernels and specification in cachesweep.h)
+// ---------------------------------------------------------------------------
+//
+// The HBM memtest streams past the caches and the other sweeps stay inside a
+// CU. This one gives every workgroup a slice of device memory small enough to
+// stay in cache and runs it, one workgroup at a time on every CU, through the
+// L1, the L2, write-through and refill, global atomics, the scalar data cache
+// and a timed read stream from the L2; a second launch reads each slice from
+// another workgroup, normally on another XCD. The host recomputes each
+// workgroup's phase checksums exactly, so a bad cache is named by (XCC, SE,
+// SH, CU) and phase. Records and result are the LDS sweep's structs.
+
+#include "cachesweep.h"
+
+// 64 KiB per workgroup: with the 32 CUs of an XCD holding one workgroup each
+// that is 2 MiB live per XCD, half of its L2, and twice a CU's L1.
+#define NA_CACHE_DEFAULT_BYTES (64 * 1024)
+#define NA_CACHE_MAX_TOTAL_BYTES (1LL << 32)
+// A pass over the 64 KiB slice, eight sc1 loads in flight per thread, takes
+// about 1.2 us per workgroup (measured: 23 B/clk and CU, latency-bound), and
+// the default grid puts four workgroups on each CU in turn: a launch pair
+// measured 0.7 ms + 5.1 us per pass, so 3072 passes make it about 16 ms, the
+// other sweeps' length (profiles/cache_sweep_mi355x.txt) and past the 10 ms
+// from which the in-kernel clock estimate is reliable (see
+// NA_MFMA_DEFAULT_OUTER).
+#define NA_CACHE_DEFAULT_ITERS 3072
+
+static const char* const cs_phase_names[CS_PHASES] = {"l1",     "l2",     "wt",   "atomic",
+                                                      "scalar", "stream", "xread"};
+
+static bool cs_bytes_ok(long long slice_bytes) {
+    return slice_bytes >= CS_GRANULE && slice_bytes <= CS_MAX_BYTES &&
+           slice_bytes % CS_GRANULE == 0;
+}
+
+// The reference of one (seed, slice_bytes). The checksums are linear in the
+// sums, over the 256 threads, of what each step reads: 256 threads folding
+// c = c*G + value leave in their sum the Horner form over the per-step sums.
+struct cs_ref {
+    uint64_t base;
+    uint32_t W, steps;
+    uint64_t table_fold[CS_TABLE_STARTS];  // a wave's fold of the table, per start
+
+    cs_ref(uint64_t base_, uint32_t slice_bytes)
+        : base(base_), W(slice_bytes / 4), steps(slice_bytes / CS_GRANULE) {
+        std::vector<uint32_t> table(CS_TABLE_WORDS);
+        for (uint32_t j = 0; j < CS_TABLE_WORDS; ++j) table[j] = cs_pat(base, CS_SCALAR, j);
+        for (uint32_t s = 0; s < CS_TABLE_STARTS; ++s) {
+            uint64_t c = 0;
+            for (uint32_t j = 0; j < CS_TABLE_WORDS; ++j)
+                c = c * MS_G + table[(256 * s + j) % CS_TABLE_WORDS];
+            table_fold[s] = c;
+        }
+    }
+
+    // The sums of lo and of hi over the 256 vectors of each of the leading n
+    // steps of the slice that starts at global word g0, under pattern pat,
+    // each word through f.
+    template <typename F>
+    void step_sums(int pat, uint64_t g0, uint32_t n, F f, std::vector<uint64_t>& lo,
+                   std::vector<uint64_t>& hi) const {
+        lo.assign(n, 0), hi.assign(n, 0);
+        for (uint32_t k = 0; k < n; ++k)
+            for (uint32_t u = 0; u < 256; ++u) {
+                const uint64_t g = g0 + 4 * (uint64_t)(256 * k + u);
+                const uint64_t w0 = f(cs_pat(base, pat, g)), w1 = f(cs_pat(base, pat, g + 1)),
+                               w2 = f(cs_pat(base, pat, g + 2)), w3 = f(cs_pat(base, pat, g + 3));
+                lo[k] += w0 | (w1 << 32);
+                hi[k] += w2 | (w3 << 32);
+            }
+    }
+
+    // One pass over the steps; inverted: every word complemented, and the sum
+    // of 256 values ~x = -1 - x is -256 - their sum.
+    static void fold_pass(uint64_t& c, const std::vector<uint64_t>& lo,
+                          const std::vector<uint64_t>& hi, bool inverted) {
+        for (size_t k = 0; k < lo.size(); ++k) {
+            c = c * MS_G + (inverted ? 0 - 256 - lo[k] : lo[k]);
+            c = c * MS_G + (inverted ? 0 - 256 - hi[k] : hi[k]);
+        }
+    }
+
+    // The CS_PHASES checksums of workgroup w of `workgroups`, both launches'.
+    void expected(uint64_t w, uint64_t workgroups, int iters, uint64_t* out) const {
+        const auto plain = [](uint32_t x) { return x; };
+        const uint64_t g0 = w * W;
+        std::vector<uint64_t> lo, hi;
+        for (int p = 0; p < CS_PHASES; ++p) out[p] = 0;
+        step_sums(CS_L1, g0, std::min<uint32_t>(steps, CS_L1_BYTES / CS_GRANULE), plain, lo, hi);
+        for (int pol = 0; pol < 2; ++pol)
+            for (int pass = 0; pass < CS_L1_PASSES; ++pass) fold_pass(out[CS_L1], lo, hi, pol);
+        step_sums(CS_L2, g0, steps, plain, lo, hi);
+        for (int pol = 0; pol < 2; ++pol)
+            for (int pass = 0; pass < CS_L2_PASSES; ++pass) fold_pass(out[CS_L2], lo, hi, pol);
+        step_sums(CS_WT, g0, steps, plain, lo, hi);
+        for (int pol = 0; pol < 2; ++pol) fold_pass(out[CS_WT], lo, hi, pol);
+        step_sums(CS_ATOMIC, g0, steps, [](uint32_t a) { return (uint32_t)(a + (a >> 16)); }, lo,
+                  hi);
+        fold_pass(out[CS_ATOMIC], lo, hi, false);
+        for (uint64_t v = 0; v < MS_WAVES_PER_WG; ++v)
+            out[CS_SCALAR] += table_fold[(w + v) % CS_TABLE_STARTS];
+        step_sums(CS_STREAM, g0, steps, plain, lo, hi);
+        uint64_t total = 0;
+        for (uint32_t k = 0; k < steps; ++k) total += lo[k] + hi[k];
+        out[CS_STREAM] = (uint64_t)iters * total;
+        // xread: the pattern-5 image of the neighbour's slice
+        step_sums(CS_STREAM, (w + 1) % workgroups * W, steps, plain, lo, hi);
+        fold_pass(out[CS_XREAD], lo, hi, false);
+    }
+};
+
+// Pure host code: the CS_PHASES checksums of workgroup `workgroup` of
+// `workgroups`, in the order of the CS_* codes: l1..stream are what its
+// record of the first launch carries, xread what its record of the second
+// does. n is the room in `checksums`.
+extern "C" int na_cache_sweep_expected(unsigned long long seed, unsigned long long workgroup,
+                                       unsigned long long workgroups, long long slice_bytes,
+                                       int iters, uint64_t* checksums, int n) {
+    if (!cs_bytes_ok(slice_bytes) || iters < 1 || workgroups < 1 || workgroup >= workgroups ||
+        checksums == nullptr || n < CS_PHASES)
+        return arg_error("na_cache_sweep_expected: need slice_bytes a multiple of %d in %d..%d "
+                         "(got %lld), iters >= 1 (got %d), workgroup %llu below workgroups %llu "
+                         "and room for %d checksums (n %d)",
+                         CS_GRANULE, CS_GRANULE, CS_MAX_BYTES, slice_bytes, iters, workgroup,
+                         workgroups, CS_PHASES, n);
+    cs_ref(seed * MS_G, (uint32_t)slice_bytes).expected(workgroup, workgroups, iters, checksums);
+    return NA_OK;
+}
+
+// Both launches of `workgroups` workgroups on one stream, HIP-event timed as
+// a pair; out receives the first launch's records, then the second's.
+// Argument errors are detected before any HIP call.
+extern "C" int na_cache_sweep_run(int dev, int workgroups, long long slice_bytes, int iters,
+                                  unsigned long long seed, na_lds_record* out, long long n_out,
+                                  double* ms) {
+    if (workgroups < 1 || workgroups > NA_LDS_MAX_WORKGROUPS || !cs_bytes_ok(slice_bytes) ||
+        workgroups * slice_bytes > NA_CACHE_MAX_TOTAL_BYTES || iters < 1 ||
+        iters > NA_LDS_MAX_ITERS || out == nullptr || n_out < 2 * (long long)workgroups)
+        return arg_error("na_cache_sweep_run: need workgroups in 1..%d (got %d), slice_bytes a "
+                         "multiple of %d up to %d (got %lld), at most %lld bytes in all, iters in "
+                         "1..%d (got %d) and room for two records per workgroup (out %p, n_out "
+                         "%lld)",
+                         NA_LDS_MAX_WORKGROUPS, workgroups, CS_GRANULE, CS_MAX_BYTES, slice_bytes,
+                         NA_CACHE_MAX_TOTAL_BYTES, NA_LDS_MAX_ITERS, iters, (void*)out, n_out);
+    HIP_CHECK(hipSetDevice(dev));  // for the buffers below, ahead of sweep_launch
+    size_t alloc = 0;
+    int rc = sweep_lds_bytes(dev, &alloc);
+    if (rc != NA_OK) return rc;
+    const mt_u64 base = seed * MS_G;
+    std::vector<uint32_t> pattern(CS_TABLE_WORDS);
+    for (uint32_t j = 0; j < CS_TABLE_WORDS; ++j) pattern[j] = cs_pat(base, CS_SCALAR, j);
+    dev_buf<uint32_t> table;
+    HIP_CHECK(table.alloc(pattern.size()));
+    HIP_CHECK(hipMemcpy(table.p, pattern.data(), pattern.size() * sizeof(uint32_t),
+                        hipMemcpyHostToDevice));
+    dev_buf<unsigned char> mem;
+    HIP_CHECK(mem.alloc((size_t)workgroups * (size_t)slice_bytes));
+    return sweep_launch(dev, 2 * (size_t)workgroups, out, ms, [&](na_lds_record* records) {
+        // the whole LDS allocation: one workgroup per CU. The second launch
+        // follows the first on the same (null) stream.
+        const dim3 grid((unsigned)workgroups), block(CS_BLOCK);
+        cache_sweep_kernel<<<grid, block, alloc>>>(records, mem.p, table.p, base,
+                                                   (uint32_t)slice_bytes, iters);
+        cache_xread_kernel<<<grid, block, alloc>>>(records + workgroups, mem.p, base,
+                                                   (uint32_t)slice_bytes);
+    });
+}
+
+// Pure host code: n records, record i being workgroup i mod (n/2) of launch
+// i / (n/2). A record is bad when a checksum of its launch is not the
+// expected one, when a checksum its launch does not compute is not 0 (the
+// failing phase is that slot's; the unused eighth counts as the index), when
+// it does not carry its own index, or when its in-kernel count of bad words
+// is not zero. bad_workgroups counts the workgroups with a bad record in
+// either launch. The census, the clock and the rates come from the first
+// launch, whose stamps bracket the stream phase. Returns NA_ERR_VERIFY on any
+// bad record; *res is filled either way.
+extern "C" int na_cache_sweep_verify(const na_lds_record* recs, long long n,
+                                     long long slice_bytes, int iters, unsigned long long seed,
+                                     na_lds_sweep_result* res) {
+    if (recs == nullptr || n < 2 || n % 2 != 0 || !cs_bytes_ok(slice_bytes) || iters < 1 ||
+        res == nullptr)
+        return arg_error("na_cache_sweep_verify: need records, an even n >= 2 (got %lld), "
+                         "slice_bytes a multiple of %d in %d..%d (got %lld), iters >= 1 (got %d) "
+                         "and a result pointer",
+                         n, CS_GRANULE, CS_GRANULE, CS_MAX_BYTES, slice_bytes, iters);
+    const long long wgs = n / 2;
+    std::memset(res, 0, sizeof(*res));
+    res->workgroups = (uint64_t)wgs;
+    res->first_bad_workgroup = res->first_bad_offset = UINT64_MAX;
+    res->first_bad_phase = ~0u;
+    const cs_ref ref(seed * MS_G, (uint32_t)slice_bytes);
+    sweep_census census;
+    std::vector<double> rate;
+    std::vector<bool> wg_bad((size_t)wgs);
+    // the bad records of the phases an XCD's L2 serves: their XCC when they
+    // share one (-1: none yet, -2: several), and their CUs
+    int l2_xcc = -1;
+    std::vector<uint32_t> l2_cus;
+    long long first_bad_record = -1;
+    // a workgroup's checksums serve its records of both launches
+    std::vector<uint64_t> want((size_t)wgs * CS_PHASES);
+    for (long long i = 0; i < n; ++i) {
+        const na_lds_record& r = recs[i];
+        const long long w = i % wgs;
+        const bool second = i >= wgs;
+        const uint64_t* wants = &want[(size_t)w * CS_PHASES];
+        if (!second) {
+            ref.expected((uint64_t)w, (uint64_t)wgs, iters, &want[(size_t)w * CS_PHASES]);
+            census.see(r);
+            if (r.cycles) rate.push_back((double)iters * (double)slice_bytes / (double)r.cycles);
+        }
+        // `phase` is the one that failed; CS_PHASES: the record is malformed
+        // or only in the wrong place
+        uint32_t phase = CS_PHASES;
+        bool bad = false;
+        for (uint32_t p = 0; p < NA_LDS_PHASES && !bad; ++p) {
+            const bool computed = p < CS_PHASES && (p == CS_XREAD) == second;
+            if (r.checksum[p] != (computed ? wants[p] : 0))
+                bad = true, phase = std::min<uint32_t>(p, CS_PHASES);
+        }
+        if (!bad && r.bad_words != 0) {
+            bad = true;
+            phase = second ? (uint32_t)CS_XREAD
+                           : r.bad_phase < CS_XREAD ? r.bad_phase : (uint32_t)CS_L1;
+        }
+        if (!bad && r.workgroup != (uint64_t)w) bad = true;  // phase stays CS_PHASES: the index
+        if (!bad) continue;
+        if (!wg_bad[(size_t)w]) wg_bad[(size_t)w] = true, res->bad_workgroups++;
+        census.mark_bad(r);
+        if (phase == CS_L2 || phase == CS_WT || phase == CS_ATOMIC || phase == CS_STREAM ||
+            phase == CS_XREAD) {
+            l2_xcc = l2_xcc == -1 || l2_xcc == (int)r.xcc ? (int)r.xcc : -2;
+            const uint32_t key = ms_cu_key(r);
+            if (std::find(l2_cus.begin(), l2_cus.end(), key) == l2_cus.end()) l2_cus.push_back(key);
+        }
+        if (first_bad_record < 0) {
+            first_bad_record = i;
+            res->first_bad_workgroup = (uint64_t)w;
+            res->first_bad_phase = phase;
+            if (r.bad_words != 0 && r.bad_phase == phase) {
+                res->bad_words = r.bad_words;
+                res->first_bad_offset = r.first_bad_offset;
+                res->xor_mask = r.xor_mask;
+            }
+        }
+    }
+    res->units_seen = census.cus_seen;
+    res->bad_units = census.bad_cus;
+    res->clock_mhz = census.clock_mhz();
+    census.bad_units(res->first_bad_unit, res->bad_list, &res->listed);
+    if (!rate.empty()) {
+        res->min_bytes_per_clk = *std::min_element(rate.begin(), rate.end());
+        res->max_bytes_per_clk = *std::max_element(rate.begin(), rate.end());
+    }
+    res->median_bytes_per_clk = median_of(rate);
+    if (first_bad_record < 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    char where[128] = "", writer[96] = "", l2[96] = "";
+    if (res->first_bad_offset != UINT64_MAX)
+        std::snprintf(where, sizeof(where),
+                      ", %llu bad words, first at slice offset 0x%llx, failing bits 0x%08llx",
+                      (unsigned long long)res->bad_words,
+                      (unsigned long long)res->first_bad_offset,
+                      (unsigned long long)res->xor_mask);
+    if (res->first_bad_phase == CS_XREAD) {
+        // who wrote what the first bad workgroup read
+        const uint64_t from = (res->first_bad_workgroup + 1) % (uint64_t)wgs;
+        const na_lds_record& a = recs[from];
+        std::snprintf(writer, sizeof(writer), "; its slice was written by workgroup %llu on "
+                      "xcc%u.se%u.sh%u.cu%u",
+                      (unsigned long long)from, a.xcc, a.se, a.sh, a.cu);
+    }
+    if (l2_xcc >= 0 && l2_cus.size() >= 2)
+        std::snprintf(l2, sizeof(l2), "; the %zu CUs that failed in a phase the L2 serves are all on "
+                      "xcc%d: suspect its L2", l2_cus.size(), l2_xcc);
+    return na_error(
+        NA_ERR_VERIFY,
+        "cache sweep: %llu of %llu workgroups wrong on %llu CU(s), first workgroup %llu in "
+        "phase %s on xcc%u.se%u.sh%u.cu%u%s%s%s",
+        (unsigned long long)res->bad_workgroups, (unsigned long long)res->workgroups,
+        (unsigned long long)res->bad_units, (unsigned long long)res->first_bad_workgroup,
+        res->first_bad_phase < CS_PHASES ? cs_phase_names[res->first_bad_phase] : "index", u[0],
+        u[1], u[2], u[3], where, writer, l2);
+}
+
+// Whole sweep: one untimed warm-up pair of launches, the timed pair, the
+// verify. workgroups 0 = 4 per CU, slice_bytes 0 = NA_CACHE_DEFAULT_BYTES,
+// iters 0 = NA_CACHE_DEFAULT_ITERS. *gbs is the chip-wide rate of the stream
+// phase from the in-kernel stamps alone, as na_lds_sweep computes its figure:
+//   gbs = median_bytes_per_clk x units_seen x clock_mhz / 1000
+extern "C" int na_cache_sweep(int dev, int workgroups, long long slice_bytes, int iters,
+                              unsigned long long seed, na_lds_sweep_result* res, double* gbs) {
+    if (res == nullptr || workgroups < 0 || workgroups > NA_LDS_MAX_WORKGROUPS ||
+        (slice_bytes != 0 && !cs_bytes_ok(slice_bytes)) ||
+        workgroups * slice_bytes > NA_CACHE_MAX_TOTAL_BYTES || iters < 0 ||
+        iters > NA_LDS_MAX_ITERS)
+        return arg_error("na_cache_sweep: need workgroups in 0..%d (got %d), slice_bytes 0 or a "
+                         "multiple of %d up to %d (got %lld), at most %lld bytes in all, iters in "
+                         "0..%d (got %d) and a result pointer",
+                         NA_LDS_MAX_WORKGROUPS, workgroups, CS_GRANULE, CS_MAX_BYTES, slice_bytes,
+                         NA_CACHE_MAX_TOTAL_BYTES, NA_LDS_MAX_ITERS, iters);
+    int rc = sweep_defaults(dev, &workgroups, &iters, NA_CACHE_DEFAULT_ITERS);
+    if (rc != NA_OK) return rc;
+    if (slice_bytes == 0) slice_bytes = NA_CACHE_DEFAULT_BYTES;
+    std::vector<na_lds_record> recs(2 * (size_t)workgroups);
+    rc = sweep_twice([&] {
+        return na_cache_sweep_run(dev, workgroups, slice_bytes, iters, seed, recs.data(),
+                                  (long long)recs.size(), nullptr);
+    });
+    if (rc != NA_OK) return rc;
+    rc = na_cache_sweep_verify(recs.data(), (long long)recs.size(), slice_bytes, iters, seed, res);
     if (gbs && (rc == NA_OK || rc == NA_ERR_VERIFY))
         *gbs = res->median_bytes_per_clk * (double)res->units_seen * res->clock_mhz / 1000.0;
     return rc;

@@ -32,6 +32,10 @@
 #define NA_LDS_PHASES 8          // checksums of an LDS record (LS_* of ldssweep.h)
 #define NA_LDS_GRANULE 4096      // an explicit lds_bytes is a multiple of this,
 #define NA_LDS_MAX_BYTES (160 * 1024)  // up to the LDS of one CU
+#define NA_CACHE_PHASES 7        // checksums the cache sweep uses of an LDS record (CS_* of cachesweep.h)
+#define NA_CACHE_GRANULE 4096    // slice_bytes is a multiple of this,
+#define NA_CACHE_MAX_BYTES (1 << 20)  // up to 1 MiB
+#define NA_CACHE_TABLE_WORDS 4096     // the scalar phase's read-only table
 #define NA_VALU_PHASES 9         // checksums of a VALU record (VS_* of valusweep.h)
 #define NA_VALU_MAX_ITERS (((1 << 24) - 2048) / 2 - 1)  // the stream phase is exact up to here
 
@@ -48,10 +52,15 @@ typedef struct {
 } na_mfma_record;
 NA_ABI_SIZE(na_mfma_record, 48);
 
-// LDS sweep (ldssweep.h). One per workgroup, written by one thread.
-// cycles/realtime are the deltas of s_memtime (shader clock) and
-// s_memrealtime (100 MHz) around the stream phase. bad_phase is an LS_* code,
-// 0xFFFFFFFF when bad_words is 0, and first_bad_offset is then UINT64_MAX.
+// LDS sweep (ldssweep.h) and cache sweep (cachesweep.h). One per workgroup
+// and launch, written by one thread. The LDS sweep fills all NA_LDS_PHASES
+// checksums; the cache sweep uses the first NA_CACHE_PHASES and leaves 0 in
+// those its launch does not compute. cycles/realtime are the deltas of
+// s_memtime (shader clock) and s_memrealtime (100 MHz) around the stream
+// phase (the cache sweep's second launch: around its xread phase). bad_phase
+// is an LS_* or CS_* code, 0xFFFFFFFF when bad_words is 0, and
+// first_bad_offset is then UINT64_MAX; otherwise it is the LDS byte offset
+// for the LDS sweep, the byte offset within the slice for the cache sweep.
 typedef struct {
     uint64_t checksum[NA_LDS_PHASES];
     uint64_t bad_words, first_bad_offset, xor_mask;
@@ -96,6 +105,7 @@ typedef struct {
 } na_mfma_sweep_result;
 NA_ABI_SIZE(na_mfma_sweep_result, 232);
 
+// Of the LDS sweep and of the cache sweep.
 typedef struct {
     uint64_t workgroups, bad_workgroups;
     uint64_t units_seen, bad_units;   // distinct (xcc, se, sh, cu)
@@ -104,11 +114,13 @@ typedef struct {
     // in the kernel; otherwise 0, UINT64_MAX, 0
     uint64_t bad_words, first_bad_offset, xor_mask;
     double clock_mhz;                 // median of cycles / realtime x 100 MHz
-    // stream phase, iters * lds_bytes / cycles per workgroup: bytes per
-    // shader clock of the CU it ran on
+    // stream phase, iters * lds_bytes / cycles per workgroup (slice_bytes for
+    // the cache sweep): bytes per shader clock of the CU it ran on
     double median_bytes_per_clk, min_bytes_per_clk, max_bytes_per_clk;
     uint32_t first_bad_unit[4];       // xcc, se, sh, cu
-    uint32_t first_bad_phase;         // LS_* code; NA_LDS_PHASES = the record's index
+    // LS_* code, NA_LDS_PHASES = the record's index; for the cache sweep a
+    // CS_* code, NA_CACHE_PHASES = the record's index
+    uint32_t first_bad_phase;
     uint32_t listed;                  // entries used in bad_list
     uint32_t bad_list[NA_SWEEP_MAX_LISTED][4];  // first distinct failing (xcc, se, sh, cu)
 } na_lds_sweep_result;
@@ -217,6 +229,18 @@ int na_lds_sweep_verify(const na_lds_record* recs, long long n, long long lds_by
                         unsigned long long seed, na_lds_sweep_result* res);
 int na_lds_sweep(int dev, int workgroups, long long lds_bytes, int iters,
                  unsigned long long seed, na_lds_sweep_result* res, double* gbs);
+
+// chip-wide cache sweep: records 0..workgroups-1 are the first launch's,
+// workgroups..2*workgroups-1 the second's
+int na_cache_sweep_expected(unsigned long long seed, unsigned long long workgroup,
+                            unsigned long long workgroups, long long slice_bytes, int iters,
+                            uint64_t* checksums, int n);
+int na_cache_sweep_run(int dev, int workgroups, long long slice_bytes, int iters,
+                       unsigned long long seed, na_lds_record* out, long long n_out, double* ms);
+int na_cache_sweep_verify(const na_lds_record* recs, long long n, long long slice_bytes, int iters,
+                          unsigned long long seed, na_lds_sweep_result* res);
+int na_cache_sweep(int dev, int workgroups, long long slice_bytes, int iters,
+                   unsigned long long seed, na_lds_sweep_result* res, double* gbs);
 
 // chip-wide vector-unit sweep
 int na_valu_sweep_xlane_table(int move, int* out, int n);

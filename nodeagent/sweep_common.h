@@ -1,5 +1,5 @@
 // What the chip-wide sweep kernels of the MI355X node agent share (mfmasweep.h,
-// ldssweep.h, valusweep.h): the launch shape, the checksum multiplier, where a
+// ldssweep.h, cachesweep.h, valusweep.h): the launch shape, the checksum multiplier, where a
 // wave runs, the clock stamp around the timed phase, and how both go into a
 // record with the fields cycles, realtime, xcc, se, sh, cu (and simd). The
 // host's counterpart is "Shared host side of the chip-wide sweeps" in agent.hip.
