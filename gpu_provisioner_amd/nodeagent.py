@@ -571,6 +571,7 @@ _ABI = {
     "na_device_count": (_int, (_int_p,)),
     "na_device_info": (_int, (_int, _char_p, _int, _char_p, _int, _i64_p, _int_p, _int_p)),
     "na_hbm_bandwidth": _BANDWIDTH,
+    "na_copy_run": (_int, (_int, _void_p, _void_p, _i64, _int, _int)),
     "na_fma_selftest": _DEV,
     "na_mfma_check_run": _CHECK_RUN,
     "na_mfma_check_verify": _CHECK_VERIFY,
@@ -739,6 +740,16 @@ class NodeAgent:
         rc = self.lib.na_hbm_bandwidth(dev, bytes_, iters, ctypes.byref(out))
         self._check(rc, f"hbm_bandwidth({dev})")
         return out.value
+
+    def copy_run(self, dev: int, src: int, dst: int, bytes_: int, workgroups: int = 0,
+                 threads: int = 0) -> int:
+        """One synchronised launch of the bandwidth probe's copy kernel on
+        caller-owned device memory (``src`` and ``dst`` 16-byte aligned and
+        disjoint, ``bytes_`` a positive multiple of 16, ``workgroups`` up to
+        65535, ``threads`` a multiple of 64 up to 1024; 0 for either is the
+        probe's own 16384 x 1024). Returns the C return code (``NA_ERR_ARG``
+        for anything outside that range)."""
+        return self.lib.na_copy_run(dev, src, dst, bytes_, workgroups, threads)
 
     def fma_selftest(self, dev: int) -> bool:
         return self.lib.na_fma_selftest(dev) == 0

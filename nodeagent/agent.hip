@@ -5,7 +5,8 @@
 // trusted (and as the node.health controller's on-node evidence), this agent
 // validates the GPU stack end to end: device discovery (gfx950 arch, 288 GB
 // HBM3E), an HBM bandwidth self-test (float4 streaming copy; healthy nodes
-// reach ~6 TB/s of the 8 TB/s peak), an opt-in HBM data-integrity test
+// reach ~6 TB/s of the 8 TB/s peak; like the SDMA and peer probes it moves
+// the memtest pattern and verifies what arrived), an opt-in HBM data-integrity test
 // (pattern fill / verify+invert / verify, memtest.h), a VALU FMA correctness
 // check, single-wave MFMA checks of every matrix-core datatype and geometry
 // the ML workloads live on (one kernel template over the operand traits of
@@ -118,7 +119,20 @@ struct dev_stream {
 // independent loads in flight per thread before the stores. Measured
 // 6233 GB/s at 16384 WGs x 1024 threads — 99% of the ≈6.3 TB/s this chip
 // sustains on read+write streams.
+//
+// Supported arguments (na_copy_run checks them; tests/
+// test_nodeagent_copyprobes.py runs the edges against data): src and dst
+// 16-byte aligned and not overlapping (__restrict__ and nontemporal accesses
+// make an overlap undefined), n >= 1 vectors of 16 bytes, any grid of 1..65535
+// workgroups and any block of 64..1024 threads in whole waves. Workgroup g
+// copies vectors [g * per, min((g + 1) * per, n)), per = ceil(n / gridDim.x);
+// with n small against the grid the last workgroups start at or past n and
+// copy nothing. Neither n nor per needs to be a multiple of anything.
 typedef float f4v __attribute__((ext_vector_type(4)));  // raw vector: nt-builtin compatible
+
+// The shape na_hbm_bandwidth times, and what 0 means to na_copy_run: the
+// sweep winner, 16384 WGs × 1024 threads (the 4-deep unroll is the kernel's).
+static const int COPY_WORKGROUPS = 16384, COPY_THREADS = 1024;
 
 __global__ void copy_f4_kernel(const float4* __restrict__ src_, float4* __restrict__ dst_,
                                size_t n) {
@@ -348,26 +362,97 @@ static int timed_loop(hipStream_t stream, int iters, dev_events<2>& t, float* ms
     return NA_OK;
 }
 
+// What the three bandwidth probes check before any HIP call.
+static int bw_check_args(const char* fn, long long bytes, int iters, const double* gbs) {
+    if (bytes < 16 || iters < 1 || gbs == nullptr)
+        return arg_error("%s: need bytes >= 16 (got %lld), iters >= 1 (got %d) and a result "
+                         "pointer (gbs %p)",
+                         fn, bytes, iters, (const void*)gbs);
+    return NA_OK;
+}
+
+// The data a bandwidth probe moves and the check that it arrived. prime()
+// fills the first `nvec` 16-byte vectors of `src` with the memtest pattern
+// (memtest.h; seed COPY_PROBE_SEED, vector index from 0) on src_dev and those
+// of `dst` with its complement on dst_dev: memory from hipMalloc may hold the
+// pattern from an earlier run, and a copy that writes nothing must leave
+// every word wrong, not right. verify() compares `dst` with the pattern on
+// dst_dev and reports any mismatch as NA_ERR_VERIFY under `name`, with the two
+// devices when they differ. Both synchronise, and both belong outside the
+// probe's timed window. They leave dst_dev current. Defined with the memtest
+// further down, whose launch and accumulator they use.
+struct copy_probe {
+    const char* name;
+    int src_dev, dst_dev;
+    void *src, *dst;
+    size_t nvec;
+    int prime() const;
+    int verify() const;
+};
+
+// One launch of the probe's kernel; 0 workgroups or threads are the probe's own.
+static void copy_launch(const void* src, void* dst, size_t nvec, int workgroups, int threads) {
+    dim3 grid(workgroups ? workgroups : COPY_WORKGROUPS), block(threads ? threads : COPY_THREADS);
+    copy_f4_kernel<<<grid, block>>>(static_cast<const float4*>(src), static_cast<float4*>(dst),
+                                    nvec);
+}
+
+// `bytes` is rounded down to a multiple of 16: that many are copied, verified
+// and counted in *gbs.
 extern "C" int na_hbm_bandwidth(int dev, long long bytes, int iters, double* gbs) {
+    int rc = bw_check_args("na_hbm_bandwidth", bytes, iters, gbs);
+    if (rc != NA_OK) return rc;
     HIP_CHECK(hipSetDevice(dev));
     size_t n = (size_t)bytes / sizeof(float4);
     dev_buf<float4> src, dst;
     HIP_CHECK(src.alloc(n));
-    int rc = alloc_second(dst, n);
+    rc = alloc_second(dst, n);
     if (rc != NA_OK) return rc;
-    HIP_CHECK(hipMemset(src.p, 1, n * sizeof(float4)));
-    // sweep winner: 16384 WGs × 1024 threads, 4-deep in-chunk unroll
-    dim3 grid(16384), block(1024);
+    const copy_probe probe = {"hbm bandwidth", dev, dev, src.p, dst.p, n};
+    rc = probe.prime();
+    if (rc != NA_OK) return rc;
     dev_events<2> t;
     for (hipEvent_t& e : t.e) HIP_CHECK(hipEventCreate(&e));
     float ms = 0.f;
     rc = timed_loop(nullptr, iters, t, &ms, [&] {
-        copy_f4_kernel<<<grid, block>>>(src.p, dst.p, n);
+        copy_launch(src.p, dst.p, n, 0, 0);
         return hipSuccess;  // the launches go unqueried, so nothing sits between two of them
     });
     if (rc != NA_OK) return rc;
     // read + write
-    *gbs = (2.0 * (double)bytes * iters) / (ms * 1e6);
+    *gbs = (2.0 * (double)(n * sizeof(float4)) * iters) / (ms * 1e6);
+    return probe.verify();
+}
+
+// One launch of copy_f4_kernel on caller-owned device memory, synchronised
+// before returning: the kernel na_hbm_bandwidth times, at any shape, so that
+// a test can look at what it moved. workgroups == 0 and threads == 0 are the
+// probe's own 16384 and 1024. Argument errors (the kernel's supported range,
+// above it) are detected before any HIP call.
+extern "C" int na_copy_run(int dev, const void* src, void* dst, long long bytes, int workgroups,
+                           int threads) {
+    const char* fn = "na_copy_run";
+    const uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
+    if (src == nullptr || dst == nullptr || ((s | d) & 15) != 0)
+        return arg_error("%s: src %p and dst %p must be non-null and 16-byte aligned", fn, src,
+                         dst);
+    if (bytes <= 0 || (bytes & 15) != 0)
+        return arg_error("%s: bytes (%lld) must be a positive multiple of 16", fn, bytes);
+    if (threads != 0 && (threads < 64 || threads > 1024 || threads % 64 != 0))
+        return arg_error("%s: threads (%d) must be 0 (the probe's %d) or a multiple of 64 in "
+                         "64..1024",
+                         fn, threads, COPY_THREADS);
+    if (workgroups < 0 || workgroups > 65535)
+        return arg_error("%s: workgroups (%d) must be in 0..65535, 0 being the probe's %d", fn,
+                         workgroups, COPY_WORKGROUPS);
+    if ((s < d ? d - s : s - d) < (uintptr_t)bytes)
+        return arg_error("%s: src %p and dst %p overlap over bytes (%lld); the kernel takes "
+                         "disjoint ranges only",
+                         fn, src, dst, bytes);
+    HIP_CHECK(hipSetDevice(dev));
+    copy_launch(src, dst, (size_t)bytes / 16, workgroups, threads);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
     return NA_OK;
 }
 
@@ -659,13 +744,18 @@ extern "C" int na_sdma_bandwidth(int dev, long long bytes, int iters, double* gb
     // device-to-device copy through hipMemcpyAsync: the runtime routes
     // large D2D copies through the SDMA engines — the same hardware RCCL
     // leans on for xGMI peer traffic. A sick SDMA engine shows up here
-    // before any collective does.
+    // before any collective does. All of `bytes` is copied and counted; the
+    // verified part is `bytes` rounded down to a multiple of 16.
+    int rc = bw_check_args("na_sdma_bandwidth", bytes, iters, gbs);
+    if (rc != NA_OK) return rc;
     HIP_CHECK(hipSetDevice(dev));
     dev_buf<char> src, dst;
     HIP_CHECK(src.alloc((size_t)bytes));
-    int rc = alloc_second(dst, (size_t)bytes);
+    rc = alloc_second(dst, (size_t)bytes);
     if (rc != NA_OK) return rc;
-    HIP_CHECK(hipMemset(src.p, 7, (size_t)bytes));
+    const copy_probe probe = {"sdma bandwidth", dev, dev, src.p, dst.p, (size_t)bytes / 16};
+    rc = probe.prime();
+    if (rc != NA_OK) return rc;
     dev_stream stream;
     HIP_CHECK(hipStreamCreate(&stream.s));
     dev_events<2> t;  // created by timed_loop
@@ -675,10 +765,13 @@ extern "C" int na_sdma_bandwidth(int dev, long long bytes, int iters, double* gb
     });
     if (rc != NA_OK) return rc;
     *gbs = (2.0 * (double)bytes * iters) / (ms * 1e6);  // read + write
-    return NA_OK;
+    return probe.verify();
 }
 
 extern "C" int na_p2p_matrix(int n, int* out /* n*n */) {
+    if (n < 1 || out == nullptr)
+        return arg_error("na_p2p_matrix: need n >= 1 (got %d) and a result pointer (out %p)", n,
+                         (void*)out);
     for (int i = 0; i < n; ++i) {
         for (int j = 0; j < n; ++j) {
             if (i == j) {
@@ -694,13 +787,25 @@ extern "C" int na_p2p_matrix(int n, int* out /* n*n */) {
 }
 
 // Returns with `src` current on every path once it has been made so: sbuf is
-// destroyed last, and each buffer is freed with its own device current.
+// destroyed last, and each buffer is freed with its own device current. The
+// pattern is filled on `src` and verified on `dst`, each by its own device.
+// All of `bytes` is copied and counted; the verified part is `bytes` rounded
+// down to a multiple of 16.
 extern "C" int na_p2p_bandwidth(int src, int dst, long long bytes, int iters, double* gbs) {
+    int rc = bw_check_args("na_p2p_bandwidth", bytes, iters, gbs);
+    if (rc != NA_OK) return rc;
+    if (src < 0 || dst < 0 || src == dst)
+        return arg_error("na_p2p_bandwidth: need two different devices, neither negative (got src "
+                         "%d, dst %d)",
+                         src, dst);
     HIP_CHECK(hipSetDevice(src));
     dev_buf<char> sbuf(src), dbuf(dst);
     HIP_CHECK(sbuf.alloc((size_t)bytes));
     HIP_CHECK(hipSetDevice(dst));
-    int rc = alloc_second(dbuf, (size_t)bytes);
+    rc = alloc_second(dbuf, (size_t)bytes);
+    if (rc != NA_OK) return rc;
+    const copy_probe probe = {"p2p bandwidth", src, dst, sbuf.p, dbuf.p, (size_t)bytes / 16};
+    rc = probe.prime();
     if (rc != NA_OK) return rc;
     HIP_CHECK(hipSetDevice(src));
     dev_events<2> t;
@@ -711,15 +816,18 @@ extern "C" int na_p2p_bandwidth(int src, int dst, long long bytes, int iters, do
     });
     if (rc != NA_OK) return rc;
     *gbs = ((double)bytes * iters) / (ms * 1e6);
-    return NA_OK;
+    return probe.verify();
 }
 
 // ---------------------------------------------------------------------------
 // HBM data-integrity test (kernels in memtest.h)
 // ---------------------------------------------------------------------------
 //
-// The bandwidth probe above never looks at what arrived; this does. One
-// round is fill(seed+r) → verify+invert → verify(inverted): every cell is
+// The bandwidth probes above move this section's pattern and verify their
+// destination once, after the timed loop (copy_probe, defined below): that
+// catches a copy that drops, misplaces or damages data, on buffers of the
+// probe's size and at one polarity. This is the test of the memory itself.
+// One round is fill(seed+r) → verify+invert → verify(inverted): every cell is
 // read back at both polarities, and because the pattern is a bijection of
 // the vector index an aliased address line is a mismatch too. Phases are
 // separate launches over the whole region, so read-back never comes from a
@@ -786,13 +894,50 @@ static int mt_check_args(const char* fn, const void* dptr, long long bytes) {
     return NA_OK;
 }
 
-static int mt_verdict(const na_memtest_result* r) {
+// `what` opens the message: the memtest, or a bandwidth probe.
+static int mt_verdict(const char* what, const na_memtest_result* r) {
     if (r->bad_words == 0) return NA_OK;
     return na_error(NA_ERR_VERIFY,
-                    "hbm memtest: %llu bad 64-bit words in %llu bytes, first at offset 0x%llx, "
+                    "%s: %llu bad 64-bit words in %llu bytes, first at offset 0x%llx, "
                     "failing bits 0x%016llx",
-                    (unsigned long long)r->bad_words, (unsigned long long)r->bytes_tested,
+                    what, (unsigned long long)r->bad_words, (unsigned long long)r->bytes_tested,
                     (unsigned long long)r->first_bad_offset, (unsigned long long)r->xor_mask);
+}
+
+// The bandwidth probes' data (copy_probe, declared with them). The seed is
+// "MI355XBW", fixed: a probe's two buffers live for one call.
+static const mt_u64 COPY_PROBE_SEED = 0x4D49333535584257ULL;
+
+int copy_probe::prime() const {
+    HIP_CHECK(hipSetDevice(src_dev));
+    int rc = mt_launch(MT_FILL, src, nvec, 0, COPY_PROBE_SEED, 0, nullptr);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipSetDevice(dst_dev));
+    rc = mt_launch(MT_FILL, dst, nvec, 0, COPY_PROBE_SEED, 1, nullptr);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+int copy_probe::verify() const {
+    HIP_CHECK(hipSetDevice(dst_dev));
+    mt_dev_accum acc;
+    acc.d.dev = dst_dev;
+    int rc = acc.init();
+    if (rc != NA_OK) return rc;
+    rc = mt_launch(MT_VERIFY, dst, nvec, 0, COPY_PROBE_SEED, 0, acc.d.p);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipDeviceSynchronize());
+    na_memtest_result res;
+    rc = acc.read((uint64_t)nvec * 16, &res);
+    if (rc != NA_OK) return rc;
+    char what[64];
+    if (src_dev == dst_dev)
+        std::snprintf(what, sizeof(what), "%s", name);
+    else
+        std::snprintf(what, sizeof(what), "%s %d->%d", name, src_dev, dst_dev);
+    return mt_verdict(what, &res);
 }
 
 // Pointer-level calls on caller-owned device memory (16-byte aligned,
@@ -826,7 +971,7 @@ extern "C" int na_memtest_verify(int dev, void* dptr, long long bytes, unsigned 
     HIP_CHECK(hipDeviceSynchronize());
     rc = acc.read((uint64_t)bytes, out);
     if (rc != NA_OK) return rc;
-    return mt_verdict(out);
+    return mt_verdict("hbm memtest", out);
 }
 
 // Whole test on a region the agent allocates itself, in chunks of at most
@@ -902,7 +1047,7 @@ extern "C" int na_hbm_memtest_passes(int dev, long long bytes, int rounds,
             pass_gbs[ph] = phase_traffic[ph] * (double)bytes * rounds / (phase_ms[ph] * 1e6);
     }
     if (gbs) *gbs = 4.0 * (double)bytes * rounds / (total_ms * 1e6);
-    return mt_verdict(out);
+    return mt_verdict("hbm memtest", out);
 }
 
 extern "C" int na_hbm_memtest(int dev, long long bytes, int rounds, unsigned long long seed,

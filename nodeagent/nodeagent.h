@@ -156,11 +156,12 @@ extern "C" {
 
 const char* na_last_error(void);
 
-// devices, bandwidth probe, VALU self-test
+// devices, bandwidth probe and one launch of its copy kernel, VALU self-test
 int na_device_count(int* count);
 int na_device_info(int dev, char* name, int name_len, char* arch, int arch_len,
                    long long* hbm_bytes, int* cus, int* max_clock_khz);
 int na_hbm_bandwidth(int dev, long long bytes, int iters, double* gbs);
+int na_copy_run(int dev, const void* src, void* dst, long long bytes, int workgroups, int threads);
 int na_fma_selftest(int dev);
 
 // single-wave MFMA checks (kinds: NA_MFMA_* of mfma_frag.h)

@@ -239,3 +239,17 @@ def test_memtest_calls_take_64_bit_pointers(cpu_agent, ptr):
     assert rc == nodeagent.NA_ERR_ARG
     assert f"na_memtest_verify: pointer {ptr:#x} " in cpu_agent._err()
     assert f"bytes ({(1 << 35) + 8})" in cpu_agent._err()
+
+
+@pytest.mark.parametrize("ptr", [(1 << 40) + 16, 1 << 40])
+def test_copy_run_takes_64_bit_pointers_and_size(cpu_agent, ptr):
+    """Overlapping ranges, a misaligned pointer and a size that is no multiple
+    of 16 are refused by the argument check, ahead of any HIP call, so the
+    pointers are only printed, never followed."""
+    other = ptr + (1 << 33)
+    assert cpu_agent.copy_run(0, ptr, ptr + 16, 32) == nodeagent.NA_ERR_ARG
+    assert f"na_copy_run: src {ptr:#x} and dst {ptr + 16:#x} overlap" in cpu_agent._err()
+    assert cpu_agent.copy_run(0, ptr, other + 8, 32) == nodeagent.NA_ERR_ARG
+    assert f"na_copy_run: src {ptr:#x} and dst {other + 8:#x} must be" in cpu_agent._err()
+    assert cpu_agent.copy_run(0, ptr, other, (1 << 35) + 8) == nodeagent.NA_ERR_ARG
+    assert f"na_copy_run: bytes ({(1 << 35) + 8})" in cpu_agent._err()
