@@ -7,7 +7,7 @@ there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
-[--cache-sweep] [--valu-sweep]``
+[--cache-sweep] [--valu-sweep] [--load-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -154,6 +154,26 @@ VALU_SWEEP_PEAK_FLOP_PER_CLK = 64
 # borrowed from the MFMA floor above. 0 disables the floor.
 MIN_VALU_SWEEP_TFLOPS = 76.1
 
+# Chip-wide load sweep (nodeagent/loadsweep.h): the matrix-core sweep's chain
+# on four waves of every CU while the other four stream device memory through
+# LDS. The default seed is "MI355XLD"; records and results are the
+# matrix-core sweep's, one set per role.
+DEFAULT_LOAD_SWEEP_SEED = 0x4D493335_35584C44
+LOAD_SWEEP_ROLES = ("matrix", "stream")
+# nodeagent/nodeagent.h: NA_LOAD_GRANULE, NA_LOAD_MAX_BYTES
+LOAD_SWEEP_GRANULE = 16384  # slice_bytes is a multiple of this
+LOAD_SWEEP_MAX_BYTES = 16 << 20
+# Floors of the default sweep's two rates, reached together: 0.70 x the
+# 1552.5 TFLOP/s and 3543.0 GB/s medians of five processes on MI355X
+# (profiles/load_sweep_mi355x.txt; the chip held 1579 MHz under that load), the
+# rule of the floors above and with the MFMA floor's caveat: integer operands
+# held in registers, not comparable to GEMM benchmarks, and a memory stream of
+# four latency-bound waves per CU, not the chip's copy bandwidth. The
+# device-to-device spread under combined load has not been measured; 0.70 is
+# borrowed from the MFMA floor. 0 disables a floor.
+MIN_LOAD_SWEEP_TFLOPS = 1086.75
+MIN_LOAD_SWEEP_GBS = 2480.1
+
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
     ("fma_selftest", "fma_ok", "VALU FMA selftest"),
@@ -297,6 +317,43 @@ class MfmaSweepResult:
             **_shared_fields(cls, res), dtype=dtype, tflops=tflops,
             bad_simds=[tuple(res.bad_list[i]) for i in range(res.listed)],
         )
+
+
+class LoadSweepNoRoom(NodeAgentError):
+    """The load sweep's region does not fit in free device memory (busy GPU) — not a fault."""
+
+
+@dataclass
+class LoadSweepResult:
+    """Outcome of a load sweep verify: an ``MfmaSweepResult`` per role of
+    ``LOAD_SWEEP_ROLES`` (the units of ``stream`` are those its waves ran on)
+    and what the stream waves' own comparison saw, as a ``MemtestResult``
+    whose offsets are relative to the region. ``tflops`` and ``gbs`` are the
+    rates the two roles reached together, from the in-kernel clocks;
+    ``matrix.clock_mhz`` is the clock under that load; ``overlap`` is the
+    median over the workgroups of the shorter role's time over the longer's
+    (0 when a role was off). All three are 0 when only a verify was done."""
+
+    matrix: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    stream: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    mem: MemtestResult = field(default_factory=MemtestResult)
+    tflops: float = 0.0
+    gbs: float = 0.0
+    overlap: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.matrix.ok and self.stream.ok and self.mem.ok
+
+    def describe(self) -> str:
+        """One sentence per failing role, then the in-kernel comparison."""
+        parts = [
+            f"{role} waves failed under combined load: {res.describe()}"
+            for role, res in zip(LOAD_SWEEP_ROLES, (self.matrix, self.stream)) if not res.ok
+        ]
+        if not self.mem.ok:
+            parts.append(f"stream comparison: {self.mem.describe()}")
+        return "; ".join(parts)
 
 
 class LdsRecord(ctypes.Structure):
@@ -623,6 +680,16 @@ _ABI = {
     "na_valu_sweep_run": (_int, (_int, _int, _int, _u64, _P(ValuRecord), _i64, _double_p)),
     "na_valu_sweep_verify": (_int, (_P(ValuRecord), _i64, _int, _u64, _P(_ValuSweepResultC))),
     "na_valu_sweep": (_int, (_int, _int, _int, _u64, _P(_ValuSweepResultC))),
+    "na_load_sweep_stream_expected": (_int, (_u64, _u64, _i64, _int, _u64_p, _int)),
+    "na_load_sweep_run": (
+        _int, (_int, _int, _int, _int, _void_p, _i64, _int, _u64, _P(MfmaRecord), _P(MfmaRecord),
+               _i64, _P(_MemtestResultC), _double_p)),
+    "na_load_sweep_verify": (
+        _int, (_P(MfmaRecord), _P(MfmaRecord), _i64, _int, _i64, _int, _u64,
+               _P(_MfmaSweepResultC), _P(_MfmaSweepResultC))),
+    "na_load_sweep": (
+        _int, (_int, _int, _int, _int, _i64, _int, _u64, _P(_MfmaSweepResultC),
+               _P(_MfmaSweepResultC), _P(_MemtestResultC), _double_p, _double_p, _double_p)),
 }
 
 
@@ -673,6 +740,15 @@ class GPUReport:
     valu_sweep_simds_seen: int = 0
     valu_sweep_bad_waves: int = 0
     valu_sweep_trans_unchecked: bool = False
+    # chip-wide load sweep (opt-in; all "not run" by default)
+    load_sweep_tflops: float = 0.0
+    load_sweep_gbs: float = 0.0
+    load_sweep_clock_mhz: float = 0.0  # under combined load; informational, no floor
+    load_sweep_overlap: float = 0.0
+    load_sweep_units_seen: int = 0
+    load_sweep_bad_waves: int = 0  # of both roles
+    load_sweep_bad_words: int = 0
+    load_sweep_skipped: str = ""  # reason, when requested but not run
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -1332,6 +1408,114 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"VALU sweep: {res.describe()}")
 
+    # -- chip-wide load sweep ----------------------------------------------------
+
+    def load_sweep_stream_expected(self, workgroup: int, slice_bytes: int, passes: int,
+                                   seed: int = DEFAULT_LOAD_SWEEP_SEED) -> list:
+        """The checksums the four stream waves of workgroup ``workgroup`` must
+        report after ``passes`` passes over its slice of ``slice_bytes`` (a
+        multiple of 16384 up to 16 MiB). The matrix waves' are
+        ``mfma_sweep_expected`` of the same seed. Host arithmetic only; needs
+        no GPU."""
+        out = (ctypes.c_uint64 * MFMA_SWEEP_WAVES_PER_WG)()
+        rc = self.lib.na_load_sweep_stream_expected(
+            seed, workgroup, slice_bytes, passes, out, len(out))
+        self._check(rc, "load_sweep_stream_expected")
+        return list(out)
+
+    def load_sweep_run(self, dev: int, region: int, workgroups: int = 1, outer: int = 1,
+                       slice_bytes: int = LOAD_SWEEP_GRANULE, passes: int = 1,
+                       seed: int = DEFAULT_LOAD_SWEEP_SEED, dtype: str = "bf16") -> tuple:
+        """One launch of ``workgroups`` x 8 waves on the caller-owned device
+        memory at ``region``: ``workgroups * slice_bytes`` bytes already
+        filled through ``memtest_fill`` with the same seed. Four waves of a
+        workgroup run ``outer`` folds of the matrix-core sweep's chain in
+        ``dtype``, four stream its slice ``passes`` times through LDS and
+        compare every word; ``outer`` 0 or ``passes`` 0 switches that role
+        off. Returns ``(matrix, stream, mem, ms)``: two ctypes arrays of
+        ``MfmaRecord`` (record i is wave i of its role), the stream waves' own
+        comparison as a ``MemtestResult`` (a mismatch is reported there, not
+        raised) and the HIP-event time."""
+        n = max(workgroups, 0) * MFMA_SWEEP_WAVES_PER_WG
+        matrix, stream = (MfmaRecord * max(n, 1))(), (MfmaRecord * max(n, 1))()
+        mem, ms = _MemtestResultC(), ctypes.c_double(0)
+        rc = self.lib.na_load_sweep_run(
+            dev, self._matrix_code("mfma", dtype), workgroups, outer, region, slice_bytes, passes,
+            seed, matrix, stream, n, ctypes.byref(mem), ctypes.byref(ms))
+        self._check(rc, f"load_sweep_run({dev})", (NA_OK, NA_ERR_VERIFY))
+        return matrix, stream, MemtestResult(**_shared_fields(MemtestResult, mem)), ms.value
+
+    def load_sweep_verify(self, matrix, stream, outer: int, slice_bytes: int, passes: int,
+                          seed: int = DEFAULT_LOAD_SWEEP_SEED, dtype: str = "bf16") -> tuple:
+        """Compare the records of both roles against the host references.
+        Returns ``(rc, LoadSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad
+        wave, and ``na_last_error`` then names the role and unit of the
+        first. The records of a role that was off must be all zero."""
+        res_m, res_s = _MfmaSweepResultC(), _MfmaSweepResultC()
+        rc = self.lib.na_load_sweep_verify(
+            matrix, stream, len(matrix), outer, slice_bytes, passes, seed,
+            ctypes.byref(res_m), ctypes.byref(res_s))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, LoadSweepResult()
+        return rc, LoadSweepResult(MfmaSweepResult._from_c(dtype, res_m),
+                                   MfmaSweepResult._from_c(dtype, res_s))
+
+    def load_sweep(self, dev: int, dtype: str = "bf16", workgroups: int = 0, outer: int = 0,
+                   slice_bytes: int = 0, passes: int = 0,
+                   seed: int = DEFAULT_LOAD_SWEEP_SEED) -> LoadSweepResult:
+        """Run one workgroup of eight waves at a time on every CU, two waves
+        per SIMD: four on the matrix-core sweep's MFMA chain, four streaming
+        a slice of pattern-filled device memory through LDS and comparing
+        every word, so that matrix cores, LDS and HBM are busy in the same
+        cycles (0 = the default for ``workgroups``, 4 per CU, and for
+        ``outer``, ``slice_bytes``, 4 MiB, and ``passes``). Every wave is
+        verified bit-exactly against the host references. Wrong waves and
+        words come back in the result (``.ok`` False) with the units they ran
+        on, not as an exception; a region that does not fit in half of the
+        free device memory raises ``LoadSweepNoRoom``."""
+        res_m, res_s, mem = _MfmaSweepResultC(), _MfmaSweepResultC(), _MemtestResultC()
+        tflops, gbs, overlap = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        rc = self.lib.na_load_sweep(
+            dev, self._matrix_code("mfma", dtype), workgroups, outer,
+            ctypes.c_longlong(slice_bytes), passes, ctypes.c_ulonglong(seed), ctypes.byref(res_m),
+            ctypes.byref(res_s), ctypes.byref(mem), ctypes.byref(tflops), ctypes.byref(gbs),
+            ctypes.byref(overlap),
+        )
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = LoadSweepNoRoom if "does not fit" in err else NodeAgentError
+            raise cls(f"load_sweep({dev}): {err}")
+        return LoadSweepResult(
+            MfmaSweepResult._from_c(dtype, res_m), MfmaSweepResult._from_c(dtype, res_s),
+            MemtestResult(**_shared_fields(MemtestResult, mem)),
+            tflops.value, gbs.value, overlap.value,
+        )
+
+    def _run_load_sweep(self, g: GPUReport) -> None:
+        try:
+            res = self.load_sweep(g.index)
+        except LoadSweepNoRoom as e:
+            # a busy GPU must not get its node replaced for lack of free memory
+            g.load_sweep_skipped = str(e)
+            return
+        g.load_sweep_tflops = round(res.tflops, 1)
+        g.load_sweep_gbs = round(res.gbs, 1)
+        g.load_sweep_clock_mhz = round(res.matrix.clock_mhz, 1)
+        g.load_sweep_overlap = round(res.overlap, 3)
+        g.load_sweep_units_seen = res.matrix.units_seen
+        g.load_sweep_bad_waves = res.matrix.bad_waves + res.stream.bad_waves
+        g.load_sweep_bad_words = res.mem.bad_words
+        if res.tflops < MIN_LOAD_SWEEP_TFLOPS:
+            g.problems.append(
+                f"load sweep {g.load_sweep_tflops} TFLOP/s below floor {MIN_LOAD_SWEEP_TFLOPS}"
+            )
+        if res.gbs < MIN_LOAD_SWEEP_GBS:
+            g.problems.append(
+                f"load sweep {g.load_sweep_gbs} GB/s below floor {MIN_LOAD_SWEEP_GBS}"
+            )
+        if not res.ok:
+            g.problems.append(f"load sweep: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -1348,7 +1532,8 @@ class NodeAgent:
     def check(self, expect_gpus: int = 0, bw_bytes: int = 1 << 30,
               memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
               mx_sweep: bool = False, lds_sweep: bool = False,
-              valu_sweep: bool = False, cache_sweep: bool = False) -> NodeReport:
+              valu_sweep: bool = False, cache_sweep: bool = False,
+              load_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -1388,7 +1573,18 @@ class NodeAgent:
         that failed (or the XCC whose L2 is suspect), as is a stream rate
         under ``MIN_CACHE_SWEEP_GBS``. ``cache_sweep_units_seen`` below the CU
         count is reported, not a problem. False (default) makes no new
-        library call."""
+        library call.
+
+        ``load_sweep`` additionally runs the chip-wide load sweep on every
+        GPU: matrix cores, LDS and HBM of every CU busy in the same cycles. A
+        wrong matrix or stream wave is a problem that names its role and unit
+        and says that it failed under combined load, as are a mismatch seen
+        by the stream waves' own comparison and a rate under
+        ``MIN_LOAD_SWEEP_TFLOPS`` or ``MIN_LOAD_SWEEP_GBS``. If the region
+        does not fit in half of the free device memory the reason lands in
+        ``load_sweep_skipped`` and the GPU stays healthy;
+        ``load_sweep_units_seen`` below the CU count is reported, not a
+        problem. False (default) makes no new library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -1434,6 +1630,8 @@ class NodeAgent:
                     self._run_cache_sweep(g)
                 if valu_sweep:
                     self._run_valu_sweep(g)
+                if load_sweep:
+                    self._run_load_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -1579,6 +1777,16 @@ def main(argv=None) -> int:
         "XCC/SE/SH/CU/SIMD; reports the packed-f32 stream rate chip-wide and of the slowest SIMD",
     )
     ap.add_argument(
+        "--load-sweep",
+        action="store_true",
+        help="also run the chip-wide load sweep on every GPU: one workgroup of eight waves at a "
+        "time on every CU, four on the matrix-core sweep's bf16 MFMA chain while the other four "
+        "stream a 4 MiB slice of pattern-filled HBM through LDS and compare every word, so that "
+        "matrix cores, LDS and HBM are busy in the same cycles; every wave checked bit-exactly "
+        "and a wrong one attributed to its role and XCC/SE/SH/CU/SIMD; reports the rates both "
+        "roles reach together and the clock under that load",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -1597,6 +1805,7 @@ def main(argv=None) -> int:
             lds_sweep=args.lds_sweep,
             valu_sweep=args.valu_sweep,
             cache_sweep=args.cache_sweep,
+            load_sweep=args.load_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

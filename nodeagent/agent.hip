@@ -20,7 +20,9 @@
 // an opt-in chip-wide cache sweep (L1, L2, write-through, global atomics,
 // scalar cache and the cross-XCD read path from every CU, cachesweep.h),
 // an opt-in chip-wide vector-unit sweep (register file and VALU of every
-// SIMD, valusweep.h), and the xGMI peer-to-peer link matrix. The
+// SIMD, valusweep.h), an opt-in chip-wide load sweep (the matrix-core
+// sweep's chain, an LDS round trip and an HBM stream on every CU in the same
+// cycles, loadsweep.h), and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
 // sweeps" below): a further sweep starts from those.
@@ -1281,25 +1283,25 @@ static int ms_run(const ms_family& fam, int dev, int code, int workgroups, int o
     });
 }
 
-// Pure host code: record i is wave i. A wave is bad when its checksum is
-// not the expected one or it does not carry its own index. Returns
-// NA_ERR_VERIFY on any bad wave; *res is filled either way.
-static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long n, int outer,
-                     unsigned long long seed, na_mfma_sweep_result* res) {
-    if (recs == nullptr || n < 1 || outer < 1 || res == nullptr)
-        return arg_error("%s_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) and a "
-                         "result pointer",
-                         fam.prefix, n, outer);
+// The verdict over n per-wave records, for the two matrix-core families and
+// for each role of the load sweep: record i is wave i and want(i) its
+// checksum. A wave is bad when its checksum is not that or it does not carry
+// its own index; the waves of a role that did not run (`ran` false: the load
+// sweep's, when switched off) are bad unless their records are all zero, and
+// are left out of the census. Fills *res.
+template <typename WANT>
+static void ms_tally(const na_mfma_record* recs, long long n, bool ran, na_mfma_sweep_result* res,
+                     WANT want) {
+    static const na_mfma_record none = {};
     std::memset(res, 0, sizeof(*res));
     res->waves = (uint64_t)n;
     res->first_bad_wave = UINT64_MAX;
-    const uint64_t base = seed * MS_G, g2 = MS_G * MS_G;
-    const uint64_t s = ms_geometric_sum(g2 * g2, (uint64_t)outer);
     sweep_census census;
     for (long long i = 0; i < n; ++i) {
         const na_mfma_record& r = recs[i];
-        census.see(r, r.simd);
-        if (r.checksum == s * ms_wave_p_sum(base, (uint64_t)i, fam.k_len) && r.wave == (uint64_t)i)
+        if (ran) census.see(r, r.simd);
+        if (ran ? r.checksum == want(i) && r.wave == (uint64_t)i
+                : std::memcmp(&r, &none, sizeof(r)) == 0)
             continue;
         res->bad_waves++;
         if (res->first_bad_wave == UINT64_MAX) res->first_bad_wave = (uint64_t)i;
@@ -1309,6 +1311,22 @@ static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long
     res->bad_units = census.bad_cus;
     res->clock_mhz = census.clock_mhz();
     census.bad_units(res->first_bad_unit, res->bad_list, &res->listed);
+}
+
+// Pure host code: record i is wave i. A wave is bad when its checksum is
+// not the expected one or it does not carry its own index. Returns
+// NA_ERR_VERIFY on any bad wave; *res is filled either way.
+static int ms_verify(const ms_family& fam, const na_mfma_record* recs, long long n, int outer,
+                     unsigned long long seed, na_mfma_sweep_result* res) {
+    if (recs == nullptr || n < 1 || outer < 1 || res == nullptr)
+        return arg_error("%s_verify: need records, n >= 1 (got %lld), outer >= 1 (got %d) and a "
+                         "result pointer",
+                         fam.prefix, n, outer);
+    const uint64_t base = seed * MS_G, g2 = MS_G * MS_G;
+    const uint64_t s = ms_geometric_sum(g2 * g2, (uint64_t)outer);
+    ms_tally(recs, n, true, res, [&](long long i) {
+        return s * ms_wave_p_sum(base, (uint64_t)i, fam.k_len);
+    });
     if (res->bad_waves == 0) return NA_OK;
     const uint32_t* u = res->first_bad_unit;
     return na_error(NA_ERR_VERIFY,
@@ -2340,4 +2358,272 @@ extern "C" int na_valu_sweep(int dev, int workgroups, int iters, unsigned long l
     });
     if (rc != NA_OK) return rc;
     return na_valu_sweep_verify(recs.data(), (long long)recs.size(), iters, seed, res);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide load sweep (kernel and specification in loadsweep.h)
+// ---------------------------------------------------------------------------
+//
+// Every sweep above tests its unit with the rest of the chip idle, and the
+// memtest streams HBM with no MFMA in flight. A part that is marginal on
+// power delivery or timing passes all of them and miscomputes in service,
+// where matrix cores, LDS and HBM are busy in the same cycles. This sweep
+// runs one workgroup of eight waves per CU at a time: four on the
+// matrix-core sweep's MFMA chain, four streaming a slice of pattern-filled
+// device memory through LDS and comparing every word. The host recomputes
+// every wave's checksum exactly, so a wave that is wrong under load is named
+// by role and (XCC, SE, SH, CU, SIMD); the in-kernel clocks give the rates
+// both roles reach together and the clock the chip holds under that load.
+// Records and results are the matrix-core sweep's structs, one set per role;
+// the in-kernel comparison reports through the memtest's.
+
+#include "loadsweep.h"
+
+// 16 GiB per workgroup at the longest slice: about a second of a CU's share
+// of HBM, NA_MFMA_MAX_OUTER's kind of bound against a typo.
+#define NA_LOAD_MAX_PASSES 1024
+#define NA_LOAD_DEFAULT_BYTES (4 << 20)
+// Chosen on the MI355X so that both roles of a workgroup take about the same
+// time: 8192 folds are the matrix-core sweep's, and 19 passes over 4 MiB take
+// the stream waves as long beside them (about 5 ms per workgroup, overlap
+// 0.98; the default grid puts four workgroups on each CU in turn: 21.8 ms per
+// launch measured, profiles/load_sweep_mi355x.txt) — the range of the other
+// sweeps, and past the 10 ms from which the in-kernel clock estimate is
+// reliable (see NA_MFMA_DEFAULT_OUTER).
+#define NA_LOAD_DEFAULT_OUTER 8192
+#define NA_LOAD_DEFAULT_PASSES 19
+
+static bool ld_bytes_ok(long long slice_bytes) {
+    return slice_bytes >= LD_GRANULE && slice_bytes <= LD_MAX_BYTES &&
+           slice_bytes % LD_GRANULE == 0;
+}
+
+// What dtype, workgroups, outer and passes must satisfy in _run; `lo` is 0
+// where the whole-sweep entry point takes 0 as "the default".
+static bool ld_shape_ok(int dtype, int workgroups, int outer, int passes, int lo) {
+    return (dtype == 0 || dtype == 1) && workgroups >= lo &&
+           workgroups <= NA_MFMA_MAX_WORKGROUPS && outer >= 0 && outer <= NA_MFMA_MAX_OUTER &&
+           passes >= 0 && passes <= NA_LOAD_MAX_PASSES;
+}
+
+// The sums of ld_term over the vectors of workgroup `workgroup`'s slice that
+// each of its four stream waves reads in one pass.
+static void ld_stream_sums(uint64_t base, uint64_t workgroup, uint64_t vecs, uint64_t* sums) {
+    for (int q = 0; q < MS_WAVES_PER_WG; ++q) sums[q] = 0;
+    const uint64_t v0 = workgroup * vecs;
+    for (uint64_t i = 0; i < vecs; ++i) {
+        const mt_vec w = mt_pattern(v0 + i, base, 0);
+        sums[(i >> 6) & (MS_WAVES_PER_WG - 1)] += ld_term(w.x, w.y);
+    }
+}
+
+// Pure host code: the checksums of the four stream waves of one workgroup
+// after `passes` passes over its slice. n is the room in `checksums`.
+extern "C" int na_load_sweep_stream_expected(unsigned long long seed, unsigned long long workgroup,
+                                             long long slice_bytes, int passes,
+                                             uint64_t* checksums, int n) {
+    if (!ld_bytes_ok(slice_bytes) || passes < 1 || passes > NA_LOAD_MAX_PASSES ||
+        checksums == nullptr || n < MS_WAVES_PER_WG)
+        return arg_error("na_load_sweep_stream_expected: need slice_bytes a multiple of %d in "
+                         "%d..%d (got %lld), passes in 1..%d (got %d) and room for %d checksums "
+                         "(n %d)",
+                         LD_GRANULE, LD_GRANULE, LD_MAX_BYTES, slice_bytes, NA_LOAD_MAX_PASSES,
+                         passes, MS_WAVES_PER_WG, n);
+    ld_stream_sums(seed * MS_G, workgroup, (uint64_t)slice_bytes / 16, checksums);
+    for (int q = 0; q < MS_WAVES_PER_WG; ++q) checksums[q] *= (uint64_t)passes;
+    return NA_OK;
+}
+
+// One launch of `workgroups` x 8 waves on a caller-owned device region of
+// workgroups * slice_bytes bytes that holds the memtest pattern of `seed`
+// (na_memtest_fill, invert 0), HIP-event timed; matrix and stream receive the
+// 4 * workgroups records of their role, *mem what the stream waves' own
+// comparison saw. Returns NA_ERR_VERIFY when that saw a mismatch; the records
+// and *mem are filled either way. Argument errors are detected before any HIP
+// call.
+extern "C" int na_load_sweep_run(int dev, int dtype, int workgroups, int outer, void* region,
+                                 long long slice_bytes, int passes, unsigned long long seed,
+                                 na_mfma_record* matrix, na_mfma_record* stream, long long n_out,
+                                 na_memtest_result* mem, double* ms) {
+    if (!ld_shape_ok(dtype, workgroups, outer, passes, 1) || !ld_bytes_ok(slice_bytes))
+        return arg_error("na_load_sweep_run: need dtype 0 (bf16) or 1 (fp8) (got %d), workgroups "
+                         "in 1..%d (got %d), outer in 0..%d (got %d), slice_bytes a multiple of %d "
+                         "up to %d (got %lld) and passes in 0..%d (got %d)",
+                         dtype, NA_MFMA_MAX_WORKGROUPS, workgroups, NA_MFMA_MAX_OUTER, outer,
+                         LD_GRANULE, LD_MAX_BYTES, slice_bytes, NA_LOAD_MAX_PASSES, passes);
+    if (outer == 0 && passes == 0)
+        return arg_error("na_load_sweep_run: outer and passes are both 0: no role to run");
+    if (region == nullptr || ((uintptr_t)region & 15) != 0 || matrix == nullptr ||
+        stream == nullptr || mem == nullptr || n_out < (long long)workgroups * MS_WAVES_PER_WG)
+        return arg_error("na_load_sweep_run: need a 16-byte aligned region (%p), room for 4 "
+                         "records per workgroup and role (matrix %p, stream %p, n_out %lld) and a "
+                         "memtest result pointer (mem %p)",
+                         region, (void*)matrix, (void*)stream, n_out, (void*)mem);
+    HIP_CHECK(hipSetDevice(dev));  // for the accumulator below, ahead of sweep_launch
+    size_t lds_bytes = 0;
+    int rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes < LD_LDS_BYTES)
+        return arg_error("na_load_sweep_run: the device's %zu-byte per-workgroup LDS allocation "
+                         "is under the %d bytes the stream waves use",
+                         lds_bytes, LD_LDS_BYTES);
+    mt_dev_accum acc;
+    rc = acc.init();
+    if (rc != NA_OK) return rc;
+    static void (*const kernels[2])(na_mfma_record*, na_mfma_record*, const mt_vec*, mt_u64, int,
+                                    uint32_t, int, mt_accum*) = {load_sweep_kernel<MS_BF16>,
+                                                                 load_sweep_kernel<MS_FP8>};
+    // one device array, the matrix records ahead of the stream records
+    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
+    std::vector<na_mfma_record> both(2 * n);
+    rc = sweep_launch(dev, 2 * n, both.data(), ms, [&](na_mfma_record* records) {
+        kernels[dtype]<<<dim3((unsigned)workgroups), dim3(LD_BLOCK), lds_bytes>>>(
+            records, records + n, static_cast<const mt_vec*>(region), seed * MS_G, outer,
+            (uint32_t)(slice_bytes / LD_GRANULE), passes, acc.d.p);
+    });
+    if (rc != NA_OK) return rc;
+    std::copy(both.begin(), both.begin() + n, matrix);
+    std::copy(both.begin() + n, both.end(), stream);
+    rc = acc.read(passes ? (uint64_t)workgroups * (uint64_t)slice_bytes : 0, mem);
+    if (rc != NA_OK) return rc;
+    return mt_verdict("load sweep", mem);
+}
+
+// Pure host code: n records per role, record i being wave i of its role
+// (workgroup i / 4). The rules are the matrix-core sweep's (ms_tally), per
+// role; the records of a role that is off (outer 0, passes 0) must be all
+// zero. Returns NA_ERR_VERIFY on any bad wave; both results are filled either
+// way.
+extern "C" int na_load_sweep_verify(const na_mfma_record* matrix, const na_mfma_record* stream,
+                                    long long n, int outer, long long slice_bytes, int passes,
+                                    unsigned long long seed, na_mfma_sweep_result* matrix_res,
+                                    na_mfma_sweep_result* stream_res) {
+    if (matrix == nullptr || stream == nullptr || n < MS_WAVES_PER_WG ||
+        n % MS_WAVES_PER_WG != 0 || !ld_shape_ok(0, 1, outer, passes, 1) ||
+        !ld_bytes_ok(slice_bytes) || matrix_res == nullptr || stream_res == nullptr)
+        return arg_error("na_load_sweep_verify: need the records of both roles, n a positive "
+                         "multiple of 4 (got %lld), outer in 0..%d (got %d), slice_bytes a multiple "
+                         "of %d up to %d (got %lld), passes in 0..%d (got %d) and two result "
+                         "pointers",
+                         n, NA_MFMA_MAX_OUTER, outer, LD_GRANULE, LD_MAX_BYTES, slice_bytes,
+                         NA_LOAD_MAX_PASSES, passes);
+    if (outer == 0 && passes == 0)
+        return arg_error("na_load_sweep_verify: outer and passes are both 0: no role ran");
+    const uint64_t base = seed * MS_G;
+    ms_tally(matrix, n, outer != 0, matrix_res, [&](long long i) {
+        uint64_t want = 0;
+        (void)ms_expected(ms_mfma, seed, (uint64_t)i, outer, &want);  // outer >= 1 here
+        return want;
+    });
+    uint64_t sums[MS_WAVES_PER_WG] = {};
+    ms_tally(stream, n, passes != 0, stream_res, [&](long long i) {
+        if (i % MS_WAVES_PER_WG == 0)  // the records come in order: once per workgroup
+            ld_stream_sums(base, (uint64_t)i / MS_WAVES_PER_WG, (uint64_t)slice_bytes / 16, sums);
+        return (uint64_t)passes * sums[i % MS_WAVES_PER_WG];
+    });
+    if (matrix_res->bad_waves == 0 && stream_res->bad_waves == 0) return NA_OK;
+    const bool first_is_matrix = matrix_res->bad_waves != 0;
+    const na_mfma_sweep_result* first = first_is_matrix ? matrix_res : stream_res;
+    const uint32_t* u = first->first_bad_unit;
+    return na_error(NA_ERR_VERIFY,
+                    "load sweep: %llu of %llu matrix waves and %llu of %llu stream waves wrong "
+                    "under combined load on %llu and %llu CU(s), first %s wave %llu on "
+                    "xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)matrix_res->bad_waves,
+                    (unsigned long long)matrix_res->waves,
+                    (unsigned long long)stream_res->bad_waves,
+                    (unsigned long long)stream_res->waves,
+                    (unsigned long long)matrix_res->bad_units,
+                    (unsigned long long)stream_res->bad_units,
+                    first_is_matrix ? "matrix" : "stream",
+                    (unsigned long long)first->first_bad_wave, u[0], u[1], u[2], u[3], u[4]);
+}
+
+// The chip-wide rate of one role from the in-kernel stamps alone, as the VALU
+// and cache sweeps compute theirs: the median wave's work per shader clock,
+// on the four waves of that role on every CU that took part, at the median
+// measured clock. `work` is one wave's, `per_mhz` scales work x MHz to the
+// unit reported.
+static double ld_rate(const na_mfma_record* recs, size_t n, double work,
+                      const na_mfma_sweep_result* res, double per_mhz) {
+    std::vector<double> rate;
+    for (size_t i = 0; i < n; ++i)
+        if (recs[i].cycles) rate.push_back(work / (double)recs[i].cycles);
+    return median_of(rate) * MS_WAVES_PER_WG * (double)res->units_seen * res->clock_mhz / per_mhz;
+}
+
+// Whole sweep on a region the agent allocates and fills itself: one untimed
+// warm-up launch, the timed launch, the verify. 0 = default for workgroups
+// (4 per CU), outer, slice_bytes and passes, so both roles run; the roles
+// alone are reached through na_load_sweep_run. *tflops and *gbs are the
+// rates the two roles reach together (ld_rate), matrix_res->clock_mhz the
+// clock under that load, *overlap the median over the workgroups of
+// min(Tm, Ts) / max(Tm, Ts), Tm and Ts being the longest realtime among the
+// workgroup's matrix waves and among its stream waves. A region over half of
+// the free device memory, or one that cannot be allocated, is NA_ERR_ARG.
+extern "C" int na_load_sweep(int dev, int dtype, int workgroups, int outer, long long slice_bytes,
+                             int passes, unsigned long long seed,
+                             na_mfma_sweep_result* matrix_res, na_mfma_sweep_result* stream_res,
+                             na_memtest_result* mem, double* tflops, double* gbs,
+                             double* overlap) {
+    if (!ld_shape_ok(dtype, workgroups, outer, passes, 0) ||
+        (slice_bytes != 0 && !ld_bytes_ok(slice_bytes)) || matrix_res == nullptr ||
+        stream_res == nullptr || mem == nullptr)
+        return arg_error("na_load_sweep: need dtype 0 (bf16) or 1 (fp8) (got %d), workgroups in "
+                         "0..%d (got %d), outer in 0..%d (got %d), slice_bytes 0 or a multiple of "
+                         "%d up to %d (got %lld), passes in 0..%d (got %d) and three result "
+                         "pointers",
+                         dtype, NA_MFMA_MAX_WORKGROUPS, workgroups, NA_MFMA_MAX_OUTER, outer,
+                         LD_GRANULE, LD_MAX_BYTES, slice_bytes, NA_LOAD_MAX_PASSES, passes);
+    int rc = sweep_defaults(dev, &workgroups, &outer, NA_LOAD_DEFAULT_OUTER);
+    if (rc != NA_OK) return rc;
+    if (passes == 0) passes = NA_LOAD_DEFAULT_PASSES;
+    if (slice_bytes == 0) slice_bytes = NA_LOAD_DEFAULT_BYTES;
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t bytes = (size_t)workgroups * (size_t)slice_bytes;
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    dev_buf<unsigned char> region;
+    if (bytes > free_b / 2 || region.alloc(bytes) != hipSuccess) {
+        (void)hipGetLastError();  // consumed here, not by a later check
+        return arg_error("na_load_sweep: the region of %zu bytes (%d workgroups x %lld) does not "
+                         "fit: %zu bytes of device memory are free and the sweep takes at most "
+                         "half",
+                         bytes, workgroups, slice_bytes, free_b);
+    }
+    rc = mt_launch(MT_FILL, region.p, bytes / 16, 0, seed, 0, nullptr);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipDeviceSynchronize());
+    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
+    std::vector<na_mfma_record> matrix(n), stream(n);
+    rc = sweep_twice([&] {
+        int run = na_load_sweep_run(dev, dtype, workgroups, outer, region.p, slice_bytes, passes,
+                                    seed, matrix.data(), stream.data(), (long long)n, mem,
+                                    nullptr);
+        return run == NA_ERR_VERIFY ? NA_OK : run;  // bad words: judged below, with the records
+    });
+    if (rc != NA_OK) return rc;
+    rc = na_load_sweep_verify(matrix.data(), stream.data(), (long long)n, outer, slice_bytes,
+                              passes, seed, matrix_res, stream_res);
+    if (rc != NA_OK && rc != NA_ERR_VERIFY) return rc;
+    if (tflops)
+        *tflops = ld_rate(matrix.data(), n,
+                          (double)outer * MS_MFMA_PER_FOLD * MS_FLOP_PER_MFMA_K * ms_mfma.k_len,
+                          matrix_res, 1e6);
+    if (gbs)
+        *gbs = ld_rate(stream.data(), n, (double)passes * (double)slice_bytes / MS_WAVES_PER_WG,
+                       stream_res, 1e3);
+    if (overlap) {
+        std::vector<double> ratio;
+        for (size_t g = 0; g < n; g += MS_WAVES_PER_WG) {
+            uint64_t tm = 0, ts = 0;
+            for (int k = 0; k < MS_WAVES_PER_WG; ++k) {
+                tm = std::max<uint64_t>(tm, matrix[g + k].realtime);
+                ts = std::max<uint64_t>(ts, stream[g + k].realtime);
+            }
+            if (tm && ts) ratio.push_back((double)std::min(tm, ts) / (double)std::max(tm, ts));
+        }
+        *overlap = median_of(ratio);
+    }
+    return rc != NA_OK ? rc : mt_verdict("load sweep", mem);
 }

@@ -54,7 +54,7 @@ __device__ __host__ inline mt_u64 mt_mix64(mt_u64 x) {
 }
 
 // `base` = seed * 0x9E3779B97F4A7C15 (hoisted to the host); `inv` = 0 or ~0.
-__device__ inline mt_vec mt_pattern(mt_u64 v, mt_u64 base, mt_u64 inv) {
+__device__ __host__ inline mt_vec mt_pattern(mt_u64 v, mt_u64 base, mt_u64 inv) {
     mt_u64 h = mt_mix64(v + base);
     mt_vec w;
     w.x = h ^ inv;

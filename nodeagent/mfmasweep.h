@@ -120,24 +120,17 @@ __device__ inline mt_u64 ms_update(mt_u64 c, f32x4 d) {
     return c;
 }
 
-#endif  // __gfx950__
-
-// records: 4 * gridDim.x entries. base = seed * G (hoisted to the host).
-// Launch with MS_BLOCK threads and more than half of the CU's LDS as dynamic
-// shared memory.
+// One wave of the sweep: the operands of global wave w, `outer` folds, the
+// checksum reduced over the wave, and lane 0's record into records[w]. The
+// body of mfma_sweep_kernel, and of the matrix waves of the load sweep
+// (loadsweep.h), which runs the same chain beside a memory stream.
 template <int DTYPE>
-__global__ void __launch_bounds__(MS_BLOCK)
-mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) {
-#if defined(__gfx950__)
-    // The dynamic LDS is a placement device and is never touched: a
-    // workgroup that holds more than half of a CU's LDS cannot share the CU
-    // with a second one, so each of its four waves has a SIMD to itself —
-    // the condition for back-to-back 16-cycle issue of this MFMA shape.
+__device__ __forceinline__ void ms_wave(na_mfma_record* __restrict__ records, mt_u64 base,
+                                        mt_u64 w, int outer) {
     typedef ms_traits<DTYPE> T;
     typedef typename T::frag frag;
     const ms_hw_where at = ms_where();
     const int l = threadIdx.x & 63;
-    const mt_u64 w = (mt_u64)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6);
 
     frag a[MS_FRAGS], b[MS_FRAGS];
     ms_fill<T>(a, b, base, w, l, std::make_integer_sequence<int, MS_FRAGS>{});
@@ -167,6 +160,23 @@ mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) 
         ms_record_simd(rec, t0, t1, at);
         records[w] = rec;
     }
+}
+
+#endif  // __gfx950__
+
+// records: 4 * gridDim.x entries. base = seed * G (hoisted to the host).
+// Launch with MS_BLOCK threads and more than half of the CU's LDS as dynamic
+// shared memory.
+template <int DTYPE>
+__global__ void __launch_bounds__(MS_BLOCK)
+mfma_sweep_kernel(na_mfma_record* __restrict__ records, mt_u64 base, int outer) {
+#if defined(__gfx950__)
+    // The dynamic LDS is a placement device and is never touched: a
+    // workgroup that holds more than half of a CU's LDS cannot share the CU
+    // with a second one, so each of its four waves has a SIMD to itself —
+    // the condition for back-to-back 16-cycle issue of this MFMA shape.
+    ms_wave<DTYPE>(records, base, (mt_u64)blockIdx.x * MS_WAVES_PER_WG + (threadIdx.x >> 6),
+                   outer);
 #else
     // wrong arch: a checksum no reference produces, so verification fails
     if ((threadIdx.x & 63) == 0) {

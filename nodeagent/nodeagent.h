@@ -38,6 +38,8 @@
 #define NA_CACHE_TABLE_WORDS 4096     // the scalar phase's read-only table
 #define NA_VALU_PHASES 9         // checksums of a VALU record (VS_* of valusweep.h)
 #define NA_VALU_MAX_ITERS (((1 << 24) - 2048) / 2 - 1)  // the stream phase is exact up to here
+#define NA_LOAD_GRANULE 16384    // the load sweep's slice_bytes is a multiple of this,
+#define NA_LOAD_MAX_BYTES (16 << 20)  // up to 16 MiB
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -45,7 +47,10 @@
 
 // Matrix-core sweep (mfmasweep.h). One per wave, written by one lane.
 // cycles/realtime are the deltas of s_memtime (shader clock) and
-// s_memrealtime (100 MHz) around the fold loop.
+// s_memrealtime (100 MHz) around the fold loop. The load sweep (loadsweep.h)
+// leaves the same record for each of its matrix waves and, with the clocks
+// around the stream loop, for each of its stream waves; a wave of a role that
+// is switched off leaves it all zero.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -254,6 +259,23 @@ int na_valu_sweep_verify(const na_valu_record* recs, long long n, int iters,
                          unsigned long long seed, na_valu_sweep_result* res);
 int na_valu_sweep(int dev, int workgroups, int iters, unsigned long long seed,
                   na_valu_sweep_result* res);
+
+// chip-wide load sweep (matrix cores, LDS and HBM at once): dtype 0 = bf16,
+// 1 = fp8; outer 0 switches the matrix waves off, passes 0 the stream waves;
+// records and results are the matrix-core sweep's, one set per role
+int na_load_sweep_stream_expected(unsigned long long seed, unsigned long long workgroup,
+                                  long long slice_bytes, int passes, uint64_t* checksums, int n);
+int na_load_sweep_run(int dev, int dtype, int workgroups, int outer, void* region,
+                      long long slice_bytes, int passes, unsigned long long seed,
+                      na_mfma_record* matrix, na_mfma_record* stream, long long n_out,
+                      na_memtest_result* mem, double* ms);
+int na_load_sweep_verify(const na_mfma_record* matrix, const na_mfma_record* stream, long long n,
+                         int outer, long long slice_bytes, int passes, unsigned long long seed,
+                         na_mfma_sweep_result* matrix_res, na_mfma_sweep_result* stream_res);
+int na_load_sweep(int dev, int dtype, int workgroups, int outer, long long slice_bytes,
+                  int passes, unsigned long long seed, na_mfma_sweep_result* matrix_res,
+                  na_mfma_sweep_result* stream_res, na_memtest_result* mem,
+                  double* tflops, double* gbs, double* overlap);
 
 #ifdef __cplusplus
 }
