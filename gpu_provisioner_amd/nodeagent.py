@@ -7,7 +7,7 @@ there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
-[--cache-sweep] [--valu-sweep] [--load-sweep]``
+[--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -173,6 +173,21 @@ LOAD_SWEEP_MAX_BYTES = 16 << 20
 # borrowed from the MFMA floor. 0 disables a floor.
 MIN_LOAD_SWEEP_TFLOPS = 1086.75
 MIN_LOAD_SWEEP_GBS = 2480.1
+
+# Chip-wide GEMM sweep (nodeagent/gemmsweep.h): C = reps * A * B^T on hashed
+# small-integer operands through HBM, L2, LDS and the bf16 or fp8 MFMA, one
+# 256 x 256 tile per workgroup. The default seed is "MI355XGS"; records and
+# results are the matrix-core sweep's, record 4 * tile + 2 * wr + wc.
+DEFAULT_GEMM_SWEEP_SEED = 0x4D493335_35584753
+# nodeagent/nodeagent.h: NA_GEMM_TILE, NA_GEMM_BK_BF16 / NA_GEMM_BK_FP8
+GEMM_SWEEP_TILE = 256  # m and n are multiples of this
+GEMM_SWEEP_BK = {"bf16": 64, "fp8": 128}  # k is a multiple of this
+# bf16 floor of the default sweep (8192^3, 14 repetitions): 0.70 x the 818.9
+# TFLOP/s median of five processes on MI355X (profiles/gemm_sweep_mi355x.txt),
+# the rule of the floors above. The operands are small integers, which clock
+# higher than random data. The device-to-device spread has not been measured;
+# 0.70 is borrowed from the MFMA floor. 0 disables the floor.
+MIN_GEMM_SWEEP_TFLOPS = 573.2
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -354,6 +369,35 @@ class LoadSweepResult:
         if not self.mem.ok:
             parts.append(f"stream comparison: {self.mem.describe()}")
         return "; ".join(parts)
+
+
+class GemmSweepNoRoom(NodeAgentError):
+    """The GEMM sweep's operands do not fit in free device memory (busy GPU) — not a fault."""
+
+
+@dataclass
+class GemmSweepResult:
+    """Outcome of a GEMM sweep verify: the matrix-core sweep's result over
+    the 4 waves per 256 x 256 tile of an ``m`` x ``n`` C, and the rate of the
+    timed launch (0 when only a verify was done)."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    m: int = 0
+    n: int = 0
+    tflops: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong wave by unit, tile and sub-tile."""
+        w = self.sweep.first_bad_wave
+        tile, nt = w // 4, max(self.n // GEMM_SWEEP_TILE, 1)
+        return (
+            f"{self.sweep.describe()}; first wave {w} on {mfma_unit_name(self.sweep.bad_simds[0])}"
+            f" computed tile ({tile // nt},{tile % nt}) sub-tile ({w >> 1 & 1},{w & 1})"
+        )
 
 
 class LdsRecord(ctypes.Structure):
@@ -690,6 +734,15 @@ _ABI = {
     "na_load_sweep": (
         _int, (_int, _int, _int, _int, _i64, _int, _u64, _P(_MfmaSweepResultC),
                _P(_MfmaSweepResultC), _P(_MemtestResultC), _double_p, _double_p, _double_p)),
+    "na_gemm_sweep_fill": (_int, (_int, _int, _void_p, _void_p, _i64, _i64, _i64, _u64)),
+    "na_gemm_sweep_expected": (_int, (_u64, _i64, _i64, _i64, _int, _u64_p, _i64)),
+    "na_gemm_sweep_run": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _i64, _i64, _i64, _int, _u64,
+               _P(MfmaRecord), _i64, _double_p)),
+    "na_gemm_sweep_verify": (
+        _int, (_P(MfmaRecord), _i64, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC))),
+    "na_gemm_sweep": (
+        _int, (_int, _int, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
 }
 
 
@@ -749,6 +802,12 @@ class GPUReport:
     load_sweep_bad_waves: int = 0  # of both roles
     load_sweep_bad_words: int = 0
     load_sweep_skipped: str = ""  # reason, when requested but not run
+    # chip-wide GEMM sweep (opt-in; all "not run" by default)
+    gemm_sweep_tflops: float = 0.0
+    gemm_sweep_clock_mhz: float = 0.0  # informational, no floor
+    gemm_sweep_units_seen: int = 0
+    gemm_sweep_bad_waves: int = 0
+    gemm_sweep_skipped: str = ""  # reason, when requested but not run
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -1516,6 +1575,90 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"load sweep: {res.describe()}")
 
+    # -- chip-wide GEMM sweep ----------------------------------------------------
+
+    def gemm_sweep_fill(self, dev: int, a: int, b: int, m: int, n: int, k: int,
+                        seed: int = DEFAULT_GEMM_SWEEP_SEED, dtype: str = "bf16") -> None:
+        """Write the hashed operands A (``m`` x ``k``) and B (``n`` x ``k``),
+        K-contiguous in ``dtype``, into the caller-owned device memory at
+        ``a`` and ``b``."""
+        rc = self.lib.na_gemm_sweep_fill(dev, self._matrix_code("mfma", dtype), a, b, m, n, k, seed)
+        self._check(rc, f"gemm_sweep_fill({dev})")
+
+    def gemm_sweep_expected(self, m: int, n: int, k: int, reps: int = 1,
+                            seed: int = DEFAULT_GEMM_SWEEP_SEED) -> list:
+        """The checksums of all ``4 * (m/256) * (n/256)`` waves, wave
+        ``4 * tile + 2 * wr + wc``; the same for both dtypes. Host arithmetic
+        only; needs no GPU."""
+        out = (ctypes.c_uint64 * max(m // GEMM_SWEEP_TILE * (n // GEMM_SWEEP_TILE) * 4, 1))()
+        self._check(self.lib.na_gemm_sweep_expected(seed, m, n, k, reps, out, len(out)),
+                    "gemm_sweep_expected")
+        return list(out)
+
+    def gemm_sweep_run(self, dev: int, a: int, b: int, m: int, n: int, k: int, reps: int = 1,
+                       seed: int = DEFAULT_GEMM_SWEEP_SEED, dtype: str = "bf16",
+                       c: int = 0) -> tuple:
+        """One launch of one workgroup per 256 x 256 tile of ``C = reps * A *
+        B^T`` on the operands at ``a`` and ``b`` (``gemm_sweep_fill`` of the
+        same seed, dtype and shape). ``c``, when not 0, is device memory for
+        the ``m`` x ``n`` float32 result. Returns ``(records, ms)``: a ctypes
+        array of ``MfmaRecord`` and the HIP-event time."""
+        recs = (MfmaRecord * max(m // GEMM_SWEEP_TILE * (n // GEMM_SWEEP_TILE) * 4, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_gemm_sweep_run(
+            dev, self._matrix_code("mfma", dtype), a, b, c or None, m, n, k, reps, seed, recs,
+            len(recs), ctypes.byref(ms))
+        self._check(rc, f"gemm_sweep_run({dev})")
+        return recs, ms.value
+
+    def gemm_sweep_verify(self, recs, m: int, n: int, k: int, reps: int = 1,
+                          seed: int = DEFAULT_GEMM_SWEEP_SEED, dtype: str = "bf16") -> tuple:
+        """Compare every record's checksum against the host reference.
+        Returns ``(rc, GemmSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad
+        wave, and ``na_last_error`` then names the first by unit, tile and
+        sub-tile."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_gemm_sweep_verify(recs, len(recs), m, n, k, reps, seed, ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, GemmSweepResult()
+        return rc, GemmSweepResult(MfmaSweepResult._from_c(dtype, res), m, n)
+
+    def gemm_sweep(self, dev: int, dtype: str = "bf16", m: int = 0, n: int = 0, k: int = 0,
+                   reps: int = 0, seed: int = DEFAULT_GEMM_SWEEP_SEED) -> GemmSweepResult:
+        """Allocate and fill the operands, run ``C = reps * A * B^T`` twice
+        (the second launch timed) and verify every wave bit-exactly (0 = the
+        default: 8192 for ``m``, ``n`` and ``k``, and the ``reps`` of a 15-25
+        ms launch). Wrong waves come back in the result (``.ok`` False), not
+        as an exception; operands that do not fit in half of the free device
+        memory raise ``GemmSweepNoRoom``."""
+        res, tflops = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_gemm_sweep(dev, self._matrix_code("mfma", dtype), m, n, k, reps, seed,
+                                    ctypes.byref(res), ctypes.byref(tflops))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = GemmSweepNoRoom if "do not fit" in err else NodeAgentError
+            raise cls(f"gemm_sweep({dev}): {err}")
+        return GemmSweepResult(MfmaSweepResult._from_c(dtype, res, tflops.value),
+                               m or 8192, n or 8192, tflops.value)
+
+    def _run_gemm_sweep(self, g: GPUReport) -> None:
+        try:
+            res = self.gemm_sweep(g.index)
+        except GemmSweepNoRoom as e:
+            # a busy GPU must not get its node replaced for lack of free memory
+            g.gemm_sweep_skipped = str(e)
+            return
+        g.gemm_sweep_tflops = round(res.tflops, 1)
+        g.gemm_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+        g.gemm_sweep_units_seen = res.sweep.units_seen
+        g.gemm_sweep_bad_waves = res.sweep.bad_waves
+        if res.tflops < MIN_GEMM_SWEEP_TFLOPS:
+            g.problems.append(
+                f"GEMM sweep {g.gemm_sweep_tflops} TFLOP/s below floor {MIN_GEMM_SWEEP_TFLOPS}"
+            )
+        if not res.ok:
+            g.problems.append(f"GEMM sweep: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -1533,7 +1676,7 @@ class NodeAgent:
               memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
               mx_sweep: bool = False, lds_sweep: bool = False,
               valu_sweep: bool = False, cache_sweep: bool = False,
-              load_sweep: bool = False) -> NodeReport:
+              load_sweep: bool = False, gemm_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -1584,7 +1727,16 @@ class NodeAgent:
         does not fit in half of the free device memory the reason lands in
         ``load_sweep_skipped`` and the GPU stays healthy;
         ``load_sweep_units_seen`` below the CU count is reported, not a
-        problem. False (default) makes no new library call."""
+        problem. False (default) makes no new library call.
+
+        ``gemm_sweep`` additionally runs the chip-wide GEMM sweep on every
+        GPU: an 8192^3 bf16 matrix multiply on hashed operands through HBM,
+        L2 and LDS, every wave's checksum recomputed on the host. A wrong
+        wave is a problem that names its unit, tile and sub-tile, as is a
+        rate under ``MIN_GEMM_SWEEP_TFLOPS``. If the operands do not fit in
+        half of the free device memory the reason lands in
+        ``gemm_sweep_skipped`` and the GPU stays healthy. False (default)
+        makes no new library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -1632,6 +1784,8 @@ class NodeAgent:
                     self._run_valu_sweep(g)
                 if load_sweep:
                     self._run_load_sweep(g)
+                if gemm_sweep:
+                    self._run_gemm_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -1787,6 +1941,15 @@ def main(argv=None) -> int:
         "roles reach together and the clock under that load",
     )
     ap.add_argument(
+        "--gemm-sweep",
+        action="store_true",
+        help="also run the chip-wide GEMM sweep on every GPU: an 8192^3 bf16 matrix multiply on "
+        "hashed small-integer operands from device memory through L2 and LDS into the MFMA, one "
+        "256 x 256 tile per workgroup; every wave's checksum of its 128 x 128 sub-tile is "
+        "recomputed on the host and a wrong one attributed to its XCC/SE/SH/CU/SIMD, tile and "
+        "sub-tile; reports the GEMM rate the GPU delivers",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -1806,6 +1969,7 @@ def main(argv=None) -> int:
             valu_sweep=args.valu_sweep,
             cache_sweep=args.cache_sweep,
             load_sweep=args.load_sweep,
+            gemm_sweep=args.gemm_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

@@ -22,7 +22,9 @@
 // an opt-in chip-wide vector-unit sweep (register file and VALU of every
 // SIMD, valusweep.h), an opt-in chip-wide load sweep (the matrix-core
 // sweep's chain, an LDS round trip and an HBM stream on every CU in the same
-// cycles, loadsweep.h), and the xGMI peer-to-peer link matrix. The
+// cycles, loadsweep.h), an opt-in chip-wide GEMM sweep (a bf16 or fp8 matrix
+// multiply from device memory through L2 and LDS into the MFMA, every wave's
+// share of C checked, gemmsweep.h), and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
 // sweeps" below): a further sweep starts from those.
@@ -2626,4 +2628,236 @@ extern "C" int na_load_sweep(int dev, int dtype, int workgroups, int outer, long
         *overlap = median_of(ratio);
     }
     return rc != NA_OK ? rc : mt_verdict("load sweep", mem);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide GEMM sweep (kernels and specification in gemmsweep.h)
+// ---------------------------------------------------------------------------
+//
+// The sweeps above test the units a matrix multiply uses, never the multiply:
+// their MFMA operands stay in registers and the words they move are never
+// multiplied. This sweep computes C = reps * A * B^T on hashed small-integer
+// operands in device memory, one 256 x 256 tile per workgroup, through L2 and
+// a swizzled, double-buffered LDS into the bf16 or fp8 MFMA. Each wave leaves
+// a weighted checksum of its 128 x 128 sub-tile, which the host recomputes
+// exactly with no O(MNK) work, so a wrong wave is named by (XCC, SE, SH, CU,
+// SIMD), tile and sub-tile; the timed launch yields the GEMM rate of the chip.
+// The agent depends on no BLAS library, so the kernel is its own. Records and
+// results are the matrix-core sweep's structs.
+
+#include "gemmsweep.h"
+
+#define NA_GEMM_DEFAULT_DIM 8192
+// Chosen on the MI355X so that one launch at 8192^3 takes 15-25 ms like the
+// other sweeps: 1.42 ms (bf16) and 0.85 ms (fp8) per repetition measured, so
+// 14 and 23 give 19.0 and 18.9 ms (profiles/gemm_sweep_mi355x.txt);
+// 6 * reps * 8192 < 2^24 allows up to 341.
+static const int gs_default_reps[2] = {14, 23};
+
+static long long gs_bk(int dtype) { return dtype == MS_FP8 ? NA_GEMM_BK_FP8 : NA_GEMM_BK_BF16; }
+
+// What m, n_cols, k and reps must satisfy; bk is the dtype's, or the smaller
+// of the two where no dtype is at hand.
+static bool gs_shape_ok(long long m, long long n, long long k, int reps, long long bk) {
+    return m >= GS_TILE && m <= NA_GEMM_MAX_DIM && m % GS_TILE == 0 && n >= GS_TILE &&
+           n <= NA_GEMM_MAX_DIM && n % GS_TILE == 0 && k >= bk && k % bk == 0 && reps >= 1 &&
+           k < NA_GEMM_EXACT && 6 * (long long)reps * k < NA_GEMM_EXACT;
+}
+
+#define GS_SHAPE_WORDS                                                                          \
+    "m and n_cols multiples of %d in %d..%d (got %lld, %lld), k a positive multiple of %lld "   \
+    "(got %lld), reps >= 1 and 6 * reps * k < 2^24 (reps %d)"
+#define GS_SHAPE_ARGS(m, n, k, reps, bk) \
+    GS_TILE, GS_TILE, NA_GEMM_MAX_DIM, (long long)(m), (long long)(n), (long long)(bk), \
+        (long long)(k), reps
+
+static long long gs_records(long long m, long long n) {
+    return (m / GS_TILE) * (n / GS_TILE) * MS_WAVES_PER_WG;
+}
+
+// Every wave's checksum without O(MNK) work: the checksum of the wave that
+// owns rows R and columns S is reps * sum_k U[k] * V[k] with U[k] = sum_{i in
+// R} p_i A[i][k] and V[k] = sum_{j in S} q_j B[j][k], so one pass over A and B
+// builds U per 128-row block and V per 128-column block, and each wave costs
+// one K-long dot product.
+static void gs_expected(uint64_t base, long long m, long long n, long long k, int reps,
+                        uint64_t* out) {
+    const uint64_t mk = (uint64_t)m * (uint64_t)k, wbase = base + mk + (uint64_t)n * (uint64_t)k;
+    std::vector<uint64_t> u((size_t)(m / GS_WAVE_TILE * k)), v((size_t)(n / GS_WAVE_TILE * k));
+    for (long long i = 0; i < m; ++i) {
+        const uint64_t p = gs_weight(wbase + (uint64_t)i);
+        uint64_t* const row = &u[(size_t)(i / GS_WAVE_TILE * k)];
+        for (long long kk = 0; kk < k; ++kk)
+            row[kk] += p * (uint64_t)(int64_t)gs_element(base + (uint64_t)(i * k + kk), GS_MOD_A);
+    }
+    for (long long j = 0; j < n; ++j) {
+        const uint64_t q = gs_weight(wbase + (uint64_t)(m + j));
+        uint64_t* const row = &v[(size_t)(j / GS_WAVE_TILE * k)];
+        for (long long kk = 0; kk < k; ++kk)
+            row[kk] +=
+                q * (uint64_t)(int64_t)gs_element(base + mk + (uint64_t)(j * k + kk), GS_MOD_B);
+    }
+    const long long nt = n / GS_TILE;
+    for (long long w = 0; w < gs_records(m, n); ++w) {
+        const long long t = w / MS_WAVES_PER_WG, wr = w >> 1 & 1, wc = w & 1;
+        const uint64_t* const ur = &u[(size_t)((t / nt * 2 + wr) * k)];
+        const uint64_t* const vr = &v[(size_t)((t % nt * 2 + wc) * k)];
+        uint64_t dot = 0;
+        for (long long kk = 0; kk < k; ++kk) dot += ur[kk] * vr[kk];
+        out[w] = (uint64_t)reps * dot;
+    }
+}
+
+// Pure host code: all 4 * (m/256) * (n_cols/256) checksums, n_out exactly that.
+extern "C" int na_gemm_sweep_expected(unsigned long long seed, long long m, long long n_cols,
+                                      long long k, int reps, uint64_t* checksums,
+                                      long long n_out) {
+    if (!gs_shape_ok(m, n_cols, k, reps, NA_GEMM_BK_BF16) || checksums == nullptr ||
+        n_out != gs_records(m, n_cols))
+        return arg_error("na_gemm_sweep_expected: need " GS_SHAPE_WORDS
+                         " and room for exactly 4 checksums per tile (checksums %p, n_out %lld)",
+                         GS_SHAPE_ARGS(m, n_cols, k, reps, NA_GEMM_BK_BF16), (void*)checksums,
+                         n_out);
+    gs_expected(seed * MS_G, m, n_cols, k, reps, checksums);
+    return NA_OK;
+}
+
+// What the entry points that touch operands check, ahead of any HIP call.
+static int gs_operand_args(const char* fn, int dtype, const void* a, const void* b, long long m,
+                           long long n, long long k, int reps) {
+    if (dtype != MS_BF16 && dtype != MS_FP8)
+        return arg_error("%s: need dtype 0 (bf16) or 1 (fp8) (got %d)", fn, dtype);
+    if (!gs_shape_ok(m, n, k, reps, gs_bk(dtype)))
+        return arg_error("%s: need " GS_SHAPE_WORDS, fn, GS_SHAPE_ARGS(m, n, k, reps, gs_bk(dtype)));
+    if (a == nullptr || b == nullptr || (((uintptr_t)a | (uintptr_t)b) & 15) != 0)
+        return arg_error("%s: need 16-byte aligned operands (a %p, b %p)", fn, a, b);
+    return NA_OK;
+}
+
+// Writes A (m x k) and B (n_cols x k) of `seed` into caller-owned device
+// memory in `dtype`, K-contiguous.
+extern "C" int na_gemm_sweep_fill(int dev, int dtype, void* a, void* b, long long m,
+                                  long long n_cols, long long k, unsigned long long seed) {
+    int rc = gs_operand_args("na_gemm_sweep_fill", dtype, a, b, m, n_cols, k, 1);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t per_vec = 16 / (dtype == MS_FP8 ? 1 : 2);
+    const uint64_t a_vecs = (uint64_t)(m * k) / per_vec, b_vecs = (uint64_t)(n_cols * k) / per_vec;
+    const unsigned grid = (unsigned)((a_vecs + b_vecs + MS_BLOCK - 1) / MS_BLOCK);
+    (dtype == MS_FP8 ? gemm_fill_kernel<MS_FP8> : gemm_fill_kernel<MS_BF16>)<<<dim3(grid),
+                                                                              dim3(MS_BLOCK)>>>(
+        static_cast<mt_vec*>(a), static_cast<mt_vec*>(b), a_vecs, b_vecs, seed * MS_G);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// One launch of one workgroup per 256 x 256 tile on caller-owned operands
+// (na_gemm_sweep_fill of the same seed, dtype and shape), HIP-event timed;
+// out receives the 4 records per tile, and c, when not null, the m x n_cols
+// f32 result (the production path passes null: the store is there so that
+// tests can compare C itself). Argument errors are detected before any HIP
+// call.
+extern "C" int na_gemm_sweep_run(int dev, int dtype, const void* a, const void* b, void* c,
+                                 long long m, long long n_cols, long long k, int reps,
+                                 unsigned long long seed, na_mfma_record* out, long long n_out,
+                                 double* ms) {
+    int rc = gs_operand_args("na_gemm_sweep_run", dtype, a, b, m, n_cols, k, reps);
+    if (rc != NA_OK) return rc;
+    if (out == nullptr || n_out != gs_records(m, n_cols) || ((uintptr_t)c & 3) != 0)
+        return arg_error("na_gemm_sweep_run: need room for exactly 4 records per tile (out %p, "
+                         "n_out %lld, want %lld) and c null or 4-byte aligned (%p)",
+                         (void*)out, n_out, gs_records(m, n_cols), c);
+    size_t lds_bytes = 0;
+    rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes < GS_LDS_BYTES)
+        return arg_error("na_gemm_sweep_run: the device's %zu-byte per-workgroup LDS allocation "
+                         "is under the %d bytes of the two stages",
+                         lds_bytes, GS_LDS_BYTES);
+    const uint32_t mt = (uint32_t)(m / GS_TILE), nt = (uint32_t)(n_cols / GS_TILE);
+    const uint64_t base = seed * MS_G;
+    const uint64_t wbase = base + (uint64_t)m * (uint64_t)k + (uint64_t)n_cols * (uint64_t)k;
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        (dtype == MS_FP8 ? gemm_sweep_kernel<MS_FP8>
+                         : gemm_sweep_kernel<MS_BF16>)<<<dim3(mt * nt), dim3(MS_BLOCK),
+                                                         GS_LDS_BYTES>>>(
+            records, static_cast<const mt_vec*>(a), static_cast<const mt_vec*>(b),
+            static_cast<float*>(c), mt, nt, (uint32_t)(k / gs_bk(dtype)), (uint32_t)reps, wbase);
+    });
+}
+
+// Pure host code: record i is wave 4 * tile + 2 * wr + wc. The rules are the
+// matrix-core sweep's (ms_tally). Returns NA_ERR_VERIFY on any bad wave, and
+// the message names the first by unit, tile and sub-tile; *res is filled
+// either way.
+extern "C" int na_gemm_sweep_verify(const na_mfma_record* recs, long long n, long long m,
+                                    long long n_cols, long long k, int reps,
+                                    unsigned long long seed, na_mfma_sweep_result* res) {
+    if (!gs_shape_ok(m, n_cols, k, reps, NA_GEMM_BK_BF16) || recs == nullptr ||
+        n != gs_records(m, n_cols) || res == nullptr)
+        return arg_error("na_gemm_sweep_verify: need " GS_SHAPE_WORDS
+                         ", exactly 4 records per tile (recs %p, n %lld) and a result pointer",
+                         GS_SHAPE_ARGS(m, n_cols, k, reps, NA_GEMM_BK_BF16), (const void*)recs, n);
+    std::vector<uint64_t> want((size_t)n);
+    gs_expected(seed * MS_G, m, n_cols, k, reps, want.data());
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const unsigned long long w = res->first_bad_wave, t = w / MS_WAVES_PER_WG;
+    const unsigned long long nt = (unsigned long long)(n_cols / GS_TILE);
+    return na_error(NA_ERR_VERIFY,
+                    "gemm sweep: %llu of %llu waves wrong on %llu CU(s), first wave %llu (tile "
+                    "%llu,%llu sub-tile %llu,%llu) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, t / nt, t % nt, w >> 1 & 1, w & 1, u[0],
+                    u[1], u[2], u[3], u[4]);
+}
+
+// Whole sweep on operands the agent allocates and fills itself: one untimed
+// warm-up launch, the timed launch, the verify. 0 = default for m, n_cols, k
+// (8192 each) and reps. *tflops counts 2 * m * n_cols * k * reps FLOP over the
+// event time. Operands over half of the free device memory, or that cannot be
+// allocated, are NA_ERR_ARG.
+extern "C" int na_gemm_sweep(int dev, int dtype, long long m, long long n_cols, long long k,
+                             int reps, unsigned long long seed, na_mfma_sweep_result* res,
+                             double* tflops) {
+    if ((dtype != MS_BF16 && dtype != MS_FP8) || res == nullptr || m < 0 || n_cols < 0 || k < 0 ||
+        reps < 0)
+        return arg_error("na_gemm_sweep: need dtype 0 (bf16) or 1 (fp8) (got %d), m, n_cols, k and "
+                         "reps >= 0 (got %lld, %lld, %lld, %d) and a result pointer",
+                         dtype, m, n_cols, k, reps);
+    if (m == 0) m = NA_GEMM_DEFAULT_DIM;
+    if (n_cols == 0) n_cols = NA_GEMM_DEFAULT_DIM;
+    if (k == 0) k = NA_GEMM_DEFAULT_DIM;
+    if (reps == 0) reps = gs_default_reps[dtype];
+    if (!gs_shape_ok(m, n_cols, k, reps, gs_bk(dtype)))
+        return arg_error("na_gemm_sweep: need " GS_SHAPE_WORDS,
+                         GS_SHAPE_ARGS(m, n_cols, k, reps, gs_bk(dtype)));
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t esize = dtype == MS_FP8 ? 1 : 2;
+    const size_t a_bytes = (size_t)(m * k) * esize, b_bytes = (size_t)(n_cols * k) * esize;
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    dev_buf<unsigned char> a, b;
+    if (a_bytes + b_bytes > free_b / 2 || a.alloc(a_bytes) != hipSuccess ||
+        b.alloc(b_bytes) != hipSuccess) {
+        (void)hipGetLastError();  // consumed here, not by a later check
+        return arg_error("na_gemm_sweep: the operands of %zu bytes (%lld x %lld and %lld x %lld) "
+                         "do not fit: %zu bytes of device memory are free and the sweep takes at "
+                         "most half",
+                         a_bytes + b_bytes, m, k, n_cols, k, free_b);
+    }
+    int rc = na_gemm_sweep_fill(dev, dtype, a.p, b.p, m, n_cols, k, seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs((size_t)gs_records(m, n_cols));
+    double ms = 0.0;
+    rc = sweep_twice([&] {
+        return na_gemm_sweep_run(dev, dtype, a.p, b.p, nullptr, m, n_cols, k, reps, seed,
+                                 recs.data(), (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
+    if (tflops) *tflops = 2.0 * (double)m * (double)n_cols * (double)k * reps / (ms * 1e9);
+    return na_gemm_sweep_verify(recs.data(), (long long)recs.size(), m, n_cols, k, reps, seed,
+                                res);
 }

@@ -40,6 +40,11 @@
 #define NA_VALU_MAX_ITERS (((1 << 24) - 2048) / 2 - 1)  // the stream phase is exact up to here
 #define NA_LOAD_GRANULE 16384    // the load sweep's slice_bytes is a multiple of this,
 #define NA_LOAD_MAX_BYTES (16 << 20)  // up to 16 MiB
+#define NA_GEMM_TILE 256         // the GEMM sweep's M and N are multiples of this,
+#define NA_GEMM_MAX_DIM 65536    // up to this;
+#define NA_GEMM_BK_BF16 64       // its K is a multiple of this for bf16,
+#define NA_GEMM_BK_FP8 128       // of this for fp8 (128 bytes per row either way),
+#define NA_GEMM_EXACT (1 << 24)  // and 6 * reps * K stays under this: exact f32 integers
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -50,7 +55,9 @@
 // s_memrealtime (100 MHz) around the fold loop. The load sweep (loadsweep.h)
 // leaves the same record for each of its matrix waves and, with the clocks
 // around the stream loop, for each of its stream waves; a wave of a role that
-// is switched off leaves it all zero.
+// is switched off leaves it all zero. The GEMM sweep (gemmsweep.h) leaves it
+// for each wave of each C tile, `wave` being 4 * tile + 2 * wr + wc and the
+// clocks around the K loops.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -276,6 +283,24 @@ int na_load_sweep(int dev, int dtype, int workgroups, int outer, long long slice
                   int passes, unsigned long long seed, na_mfma_sweep_result* matrix_res,
                   na_mfma_sweep_result* stream_res, na_memtest_result* mem,
                   double* tflops, double* gbs, double* overlap);
+
+// chip-wide GEMM sweep, C = reps * A * B^T through HBM, L2 and LDS: dtype 0 =
+// bf16, 1 = fp8; a is m x k, b n_cols x k, both K-contiguous in that dtype, c
+// null or m x n_cols floats; records and results are the matrix-core sweep's,
+// record 4 * tile + 2 * wr + wc for the wave of the 128 x 128 sub-tile (wr, wc)
+// of tile ti * (n_cols / 256) + tj
+int na_gemm_sweep_fill(int dev, int dtype, void* a, void* b, long long m, long long n_cols,
+                       long long k, unsigned long long seed);
+int na_gemm_sweep_expected(unsigned long long seed, long long m, long long n_cols, long long k,
+                           int reps, uint64_t* checksums, long long n_out);
+int na_gemm_sweep_run(int dev, int dtype, const void* a, const void* b, void* c, long long m,
+                      long long n_cols, long long k, int reps, unsigned long long seed,
+                      na_mfma_record* out, long long n_out, double* ms);
+int na_gemm_sweep_verify(const na_mfma_record* recs, long long n, long long m, long long n_cols,
+                         long long k, int reps, unsigned long long seed,
+                         na_mfma_sweep_result* res);
+int na_gemm_sweep(int dev, int dtype, long long m, long long n_cols, long long k, int reps,
+                  unsigned long long seed, na_mfma_sweep_result* res, double* tflops);
 
 #ifdef __cplusplus
 }
