@@ -7,7 +7,7 @@ there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
-[--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep]``
+[--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -188,6 +188,23 @@ GEMM_SWEEP_BK = {"bf16": 64, "fp8": 128}  # k is a multiple of this
 # higher than random data. The device-to-device spread has not been measured;
 # 0.70 is borrowed from the MFMA floor. 0 disables the floor.
 MIN_GEMM_SWEEP_TFLOPS = 573.2
+
+# Chip-wide block-scaled MX GEMM sweep (nodeagent/mxgemmsweep.h): the GEMM sweep
+# on v_mfma_scale_f32_16x16x128_f8f6f4, operands in MXFP8 or MXFP4 and an E8M0
+# scale per 32 elements of every row, both from device memory. The default
+# seed is "MI355XXG"; tiles, records and results are the GEMM sweep's. The
+# format codes are MX_E4M3 and MX_E2M1 of nodeagent/mx_formats.h.
+DEFAULT_MXGEMM_SWEEP_SEED = 0x4D493335_35585847
+MXGEMM_SWEEP_FORMATS = {"fp8": 0, "fp4": 4}
+# nodeagent/nodeagent.h: NA_MXGEMM_BK_FP8 / NA_MXGEMM_BK_FP4
+MXGEMM_SWEEP_BK = {"fp8": 128, "fp4": 256}  # k is a multiple of this
+# Floors of the default sweep (8192^3, 25 and 50 repetitions) per format: 0.70 x
+# the 1495.6 and 3303.1 TFLOP/s medians of five processes on MI355X
+# (profiles/mxgemm_sweep_mi355x.txt), the rule of the floors above, with the
+# GEMM floor's caveat: small integers clock higher than random data. The
+# device-to-device spread has not been measured; 0.70 is borrowed from the MFMA
+# floor. 0 disables a floor.
+MIN_MXGEMM_SWEEP_TFLOPS = {"fp8": 1046.9, "fp4": 2312.2}
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -379,7 +396,8 @@ class GemmSweepNoRoom(NodeAgentError):
 class GemmSweepResult:
     """Outcome of a GEMM sweep verify: the matrix-core sweep's result over
     the 4 waves per 256 x 256 tile of an ``m`` x ``n`` C, and the rate of the
-    timed launch (0 when only a verify was done)."""
+    timed launch (0 when only a verify was done). The MX GEMM sweep's outcome
+    too: same tiles, same records."""
 
     sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
     m: int = 0
@@ -743,6 +761,16 @@ _ABI = {
         _int, (_P(MfmaRecord), _i64, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC))),
     "na_gemm_sweep": (
         _int, (_int, _int, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
+    "na_mxgemm_sweep_fill": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _void_p, _i64, _i64, _i64, _u64)),
+    "na_mxgemm_sweep_expected": (_int, (_u64, _i64, _i64, _i64, _int, _u64_p, _i64)),
+    "na_mxgemm_sweep_run": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _void_p, _void_p, _i64, _i64, _i64, _int,
+               _u64, _P(MfmaRecord), _i64, _double_p)),
+    "na_mxgemm_sweep_verify": (
+        _int, (_P(MfmaRecord), _i64, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC))),
+    "na_mxgemm_sweep": (
+        _int, (_int, _int, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
 }
 
 
@@ -808,6 +836,13 @@ class GPUReport:
     gemm_sweep_units_seen: int = 0
     gemm_sweep_bad_waves: int = 0
     gemm_sweep_skipped: str = ""  # reason, when requested but not run
+    # chip-wide MX GEMM sweep (opt-in; all "not run" by default)
+    mxgemm_sweep_fp8_tflops: float = 0.0
+    mxgemm_sweep_fp4_tflops: float = 0.0
+    mxgemm_sweep_clock_mhz: float = 0.0  # fp8 run; informational, no floor
+    mxgemm_sweep_units_seen: int = 0
+    mxgemm_sweep_bad_waves: int = 0  # of both formats
+    mxgemm_sweep_skipped: str = ""  # reason, when requested but not run
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -1659,6 +1694,99 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"GEMM sweep: {res.describe()}")
 
+    # -- chip-wide MX GEMM sweep -------------------------------------------------
+
+    @staticmethod
+    def _mxgemm_code(fmt: str) -> int:
+        if fmt not in MXGEMM_SWEEP_FORMATS:
+            raise NodeAgentError(
+                f"mxgemm sweep: format {fmt!r} is not one of {', '.join(MXGEMM_SWEEP_FORMATS)}")
+        return MXGEMM_SWEEP_FORMATS[fmt]
+
+    def mxgemm_sweep_fill(self, dev: int, a: int, b: int, sa: int, sb: int, m: int, n: int,
+                          k: int, seed: int = DEFAULT_MXGEMM_SWEEP_SEED, fmt: str = "fp8") -> None:
+        """Write the hashed operands A (``m`` x ``k``) and B (``n`` x ``k``),
+        K-contiguous in ``fmt`` ("fp8": a byte per element; "fp4": two per
+        byte, even k in the low nibble), and their E8M0 scales (``m`` x
+        ``k/32`` and ``n`` x ``k/32`` bytes) into the caller-owned device
+        memory at ``a``, ``b``, ``sa`` and ``sb``."""
+        rc = self.lib.na_mxgemm_sweep_fill(dev, self._mxgemm_code(fmt), a, b, sa, sb, m, n, k, seed)
+        self._check(rc, f"mxgemm_sweep_fill({dev})")
+
+    def mxgemm_sweep_expected(self, m: int, n: int, k: int, reps: int = 1,
+                              seed: int = DEFAULT_MXGEMM_SWEEP_SEED) -> list:
+        """The checksums of all ``4 * (m/256) * (n/256)`` waves, wave
+        ``4 * tile + 2 * wr + wc``; the same for both formats. Host
+        arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * max(m // GEMM_SWEEP_TILE * (n // GEMM_SWEEP_TILE) * 4, 1))()
+        self._check(self.lib.na_mxgemm_sweep_expected(seed, m, n, k, reps, out, len(out)),
+                    "mxgemm_sweep_expected")
+        return list(out)
+
+    def mxgemm_sweep_run(self, dev: int, a: int, b: int, sa: int, sb: int, m: int, n: int, k: int,
+                         reps: int = 1, seed: int = DEFAULT_MXGEMM_SWEEP_SEED, fmt: str = "fp8",
+                         c: int = 0) -> tuple:
+        """One launch of one workgroup per 256 x 256 tile of the block-scaled
+        product on the operands and scales at ``a``, ``b``, ``sa`` and ``sb``
+        (``mxgemm_sweep_fill`` of the same seed, format and shape). ``c``,
+        when not 0, is device memory for the ``m`` x ``n`` float32 result.
+        Returns ``(records, ms)`` as ``gemm_sweep_run``."""
+        recs = (MfmaRecord * max(m // GEMM_SWEEP_TILE * (n // GEMM_SWEEP_TILE) * 4, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_mxgemm_sweep_run(
+            dev, self._mxgemm_code(fmt), a, b, sa, sb, c or None, m, n, k, reps, seed, recs,
+            len(recs), ctypes.byref(ms))
+        self._check(rc, f"mxgemm_sweep_run({dev})")
+        return recs, ms.value
+
+    def mxgemm_sweep_verify(self, recs, m: int, n: int, k: int, reps: int = 1,
+                            seed: int = DEFAULT_MXGEMM_SWEEP_SEED, fmt: str = "fp8") -> tuple:
+        """As ``gemm_sweep_verify``, against the MX GEMM sweep's reference."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_mxgemm_sweep_verify(recs, len(recs), m, n, k, reps, seed,
+                                             ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, GemmSweepResult()
+        return rc, GemmSweepResult(MfmaSweepResult._from_c(fmt, res), m, n)
+
+    def mxgemm_sweep(self, dev: int, fmt: str = "fp8", m: int = 0, n: int = 0, k: int = 0,
+                     reps: int = 0, seed: int = DEFAULT_MXGEMM_SWEEP_SEED) -> GemmSweepResult:
+        """As ``gemm_sweep`` on the block-scaled instruction in ``fmt``:
+        allocate and fill operands and scales, run twice (the second launch
+        timed) and verify every wave bit-exactly (0 = the default: 8192 for
+        ``m``, ``n`` and ``k``, and the format's ``reps``). Operands that do
+        not fit in half of the free device memory raise ``GemmSweepNoRoom``."""
+        res, tflops = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_mxgemm_sweep(dev, self._mxgemm_code(fmt), m, n, k, reps, seed,
+                                      ctypes.byref(res), ctypes.byref(tflops))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = GemmSweepNoRoom if "do not fit" in err else NodeAgentError
+            raise cls(f"mxgemm_sweep({dev}, {fmt}): {err}")
+        return GemmSweepResult(MfmaSweepResult._from_c(fmt, res, tflops.value),
+                               m or 8192, n or 8192, tflops.value)
+
+    def _run_mxgemm_sweep(self, g: GPUReport) -> None:
+        for fmt in MXGEMM_SWEEP_FORMATS:
+            try:
+                res = self.mxgemm_sweep(g.index, fmt)
+            except GemmSweepNoRoom as e:
+                # a busy GPU must not get its node replaced for lack of free memory
+                g.mxgemm_sweep_skipped = str(e)
+                return
+            setattr(g, f"mxgemm_sweep_{fmt}_tflops", round(res.tflops, 1))
+            g.mxgemm_sweep_bad_waves += res.sweep.bad_waves
+            if fmt == "fp8":
+                g.mxgemm_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+                g.mxgemm_sweep_units_seen = res.sweep.units_seen
+            if res.tflops < MIN_MXGEMM_SWEEP_TFLOPS[fmt]:
+                g.problems.append(
+                    f"MX GEMM sweep {fmt} {round(res.tflops, 1)} TFLOP/s below floor "
+                    f"{MIN_MXGEMM_SWEEP_TFLOPS[fmt]}"
+                )
+            if not res.ok:
+                g.problems.append(f"MX GEMM sweep {fmt}: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -1676,7 +1804,8 @@ class NodeAgent:
               memtest_bytes: int = 0, mfma_sweep: bool = False, mx_checks: bool = False,
               mx_sweep: bool = False, lds_sweep: bool = False,
               valu_sweep: bool = False, cache_sweep: bool = False,
-              load_sweep: bool = False, gemm_sweep: bool = False) -> NodeReport:
+              load_sweep: bool = False, gemm_sweep: bool = False,
+              mxgemm_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -1736,7 +1865,15 @@ class NodeAgent:
         rate under ``MIN_GEMM_SWEEP_TFLOPS``. If the operands do not fit in
         half of the free device memory the reason lands in
         ``gemm_sweep_skipped`` and the GPU stays healthy. False (default)
-        makes no new library call."""
+        makes no new library call.
+
+        ``mxgemm_sweep`` additionally runs the chip-wide MX GEMM sweep on
+        every GPU: the same multiply on the block-scaled instruction in MXFP8
+        and MXFP4, with an E8M0 scale per 32 elements that comes from device
+        memory like the operands. A wrong wave is a problem that names its
+        format, unit, tile and sub-tile, as is a rate under the format's
+        ``MIN_MXGEMM_SWEEP_TFLOPS``; operands that do not fit land in
+        ``mxgemm_sweep_skipped``. False (default) makes no new library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -1786,6 +1923,8 @@ class NodeAgent:
                     self._run_load_sweep(g)
                 if gemm_sweep:
                     self._run_gemm_sweep(g)
+                if mxgemm_sweep:
+                    self._run_mxgemm_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -1950,6 +2089,15 @@ def main(argv=None) -> int:
         "sub-tile; reports the GEMM rate the GPU delivers",
     )
     ap.add_argument(
+        "--mxgemm-sweep",
+        action="store_true",
+        help="also run the chip-wide MX GEMM sweep on every GPU: the GEMM sweep's 8192^3 multiply "
+        "on the block-scaled 16x16x128 instruction in MXFP8 and MXFP4, operands and their E8M0 "
+        "scales (one per 32 elements) both from device memory; every wave checked as in "
+        "--gemm-sweep, so a wrong scale path or a CU that cannot feed the instruction from LDS "
+        "is attributed to its XCC/SE/SH/CU/SIMD, tile and sub-tile; reports the rate per format",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -1970,6 +2118,7 @@ def main(argv=None) -> int:
             cache_sweep=args.cache_sweep,
             load_sweep=args.load_sweep,
             gemm_sweep=args.gemm_sweep,
+            mxgemm_sweep=args.mxgemm_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

@@ -24,7 +24,9 @@
 // sweep's chain, an LDS round trip and an HBM stream on every CU in the same
 // cycles, loadsweep.h), an opt-in chip-wide GEMM sweep (a bf16 or fp8 matrix
 // multiply from device memory through L2 and LDS into the MFMA, every wave's
-// share of C checked, gemmsweep.h), and the xGMI peer-to-peer link matrix. The
+// share of C checked, gemmsweep.h), the same on the block-scaled instruction
+// in MXFP8 and MXFP4 with E8M0 scales that come from device memory too
+// (mxgemmsweep.h), and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
 // sweeps" below): a further sweep starts from those.
@@ -2679,23 +2681,22 @@ static long long gs_records(long long m, long long n) {
 // owns rows R and columns S is reps * sum_k U[k] * V[k] with U[k] = sum_{i in
 // R} p_i A[i][k] and V[k] = sum_{j in S} q_j B[j][k], so one pass over A and B
 // builds U per 128-row block and V per 128-column block, and each wave costs
-// one K-long dot product.
-static void gs_expected(uint64_t base, long long m, long long n, long long k, int reps,
-                        uint64_t* out) {
-    const uint64_t mk = (uint64_t)m * (uint64_t)k, wbase = base + mk + (uint64_t)n * (uint64_t)k;
+// one K-long dot product. a_at(i, kk) and b_at(j, kk) are the operands' values
+// (the MX GEMM sweep's with their block scales folded in), wbase is where the
+// weights start in the hashed sequence.
+template <typename A_AT, typename B_AT>
+static void gs_expected_of(uint64_t wbase, long long m, long long n, long long k, int reps,
+                           A_AT a_at, B_AT b_at, uint64_t* out) {
     std::vector<uint64_t> u((size_t)(m / GS_WAVE_TILE * k)), v((size_t)(n / GS_WAVE_TILE * k));
     for (long long i = 0; i < m; ++i) {
         const uint64_t p = gs_weight(wbase + (uint64_t)i);
         uint64_t* const row = &u[(size_t)(i / GS_WAVE_TILE * k)];
-        for (long long kk = 0; kk < k; ++kk)
-            row[kk] += p * (uint64_t)(int64_t)gs_element(base + (uint64_t)(i * k + kk), GS_MOD_A);
+        for (long long kk = 0; kk < k; ++kk) row[kk] += p * (uint64_t)(int64_t)a_at(i, kk);
     }
     for (long long j = 0; j < n; ++j) {
         const uint64_t q = gs_weight(wbase + (uint64_t)(m + j));
         uint64_t* const row = &v[(size_t)(j / GS_WAVE_TILE * k)];
-        for (long long kk = 0; kk < k; ++kk)
-            row[kk] +=
-                q * (uint64_t)(int64_t)gs_element(base + mk + (uint64_t)(j * k + kk), GS_MOD_B);
+        for (long long kk = 0; kk < k; ++kk) row[kk] += q * (uint64_t)(int64_t)b_at(j, kk);
     }
     const long long nt = n / GS_TILE;
     for (long long w = 0; w < gs_records(m, n); ++w) {
@@ -2706,6 +2707,20 @@ static void gs_expected(uint64_t base, long long m, long long n, long long k, in
         for (long long kk = 0; kk < k; ++kk) dot += ur[kk] * vr[kk];
         out[w] = (uint64_t)reps * dot;
     }
+}
+
+static void gs_expected(uint64_t base, long long m, long long n, long long k, int reps,
+                        uint64_t* out) {
+    const uint64_t mk = (uint64_t)m * (uint64_t)k;
+    gs_expected_of(
+        base + mk + (uint64_t)n * (uint64_t)k, m, n, k, reps,
+        [&](long long i, long long kk) {
+            return gs_element(base + (uint64_t)(i * k + kk), GS_MOD_A);
+        },
+        [&](long long j, long long kk) {
+            return gs_element(base + mk + (uint64_t)(j * k + kk), GS_MOD_B);
+        },
+        out);
 }
 
 // Pure host code: all 4 * (m/256) * (n_cols/256) checksums, n_out exactly that.
@@ -2787,10 +2802,43 @@ extern "C" int na_gemm_sweep_run(int dev, int dtype, const void* a, const void* 
     });
 }
 
-// Pure host code: record i is wave 4 * tile + 2 * wr + wc. The rules are the
-// matrix-core sweep's (ms_tally). Returns NA_ERR_VERIFY on any bad wave, and
-// the message names the first by unit, tile and sub-tile; *res is filled
-// either way.
+// The records against `want` by the matrix-core sweep's rules (ms_tally), for
+// this sweep and the MX GEMM sweep: NA_ERR_VERIFY on any bad wave, with a
+// message that names the first by unit, tile and sub-tile.
+static int gs_verdict(const char* sweep, const na_mfma_record* recs, long long n, long long n_cols,
+                      const std::vector<uint64_t>& want, na_mfma_sweep_result* res) {
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const unsigned long long w = res->first_bad_wave, t = w / MS_WAVES_PER_WG;
+    const unsigned long long nt = (unsigned long long)(n_cols / GS_TILE);
+    return na_error(NA_ERR_VERIFY,
+                    "%s: %llu of %llu waves wrong on %llu CU(s), first wave %llu (tile "
+                    "%llu,%llu sub-tile %llu,%llu) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    sweep, (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, t / nt, t % nt, w >> 1 & 1, w & 1, u[0],
+                    u[1], u[2], u[3], u[4]);
+}
+
+// Device memory for a sweep's operands, sizes[i] bytes into bufs[i]: over half
+// of the free device memory, or not to be had, is NA_ERR_ARG ("do not fit":
+// callers record a skip, not a fault).
+static int gs_alloc(const char* fn, dev_buf<unsigned char>* bufs, const size_t* sizes, int count,
+                    long long m, long long n, long long k) {
+    size_t free_b = 0, total_b = 0, all = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    for (int i = 0; i < count; ++i) all += sizes[i];
+    bool ok = all <= free_b / 2;
+    for (int i = 0; ok && i < count; ++i) ok = bufs[i].alloc(sizes[i]) == hipSuccess;
+    if (ok) return NA_OK;
+    (void)hipGetLastError();  // consumed here, not by a later check
+    return arg_error("%s: the operands of %zu bytes (%lld x %lld and %lld x %lld) do not fit: %zu "
+                     "bytes of device memory are free and the sweep takes at most half",
+                     fn, all, m, k, n, k, free_b);
+}
+
+// Pure host code: record i is wave 4 * tile + 2 * wr + wc. Returns
+// NA_ERR_VERIFY on any bad wave (gs_verdict); *res is filled either way.
 extern "C" int na_gemm_sweep_verify(const na_mfma_record* recs, long long n, long long m,
                                     long long n_cols, long long k, int reps,
                                     unsigned long long seed, na_mfma_sweep_result* res) {
@@ -2801,17 +2849,7 @@ extern "C" int na_gemm_sweep_verify(const na_mfma_record* recs, long long n, lon
                          GS_SHAPE_ARGS(m, n_cols, k, reps, NA_GEMM_BK_BF16), (const void*)recs, n);
     std::vector<uint64_t> want((size_t)n);
     gs_expected(seed * MS_G, m, n_cols, k, reps, want.data());
-    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
-    if (res->bad_waves == 0) return NA_OK;
-    const uint32_t* u = res->first_bad_unit;
-    const unsigned long long w = res->first_bad_wave, t = w / MS_WAVES_PER_WG;
-    const unsigned long long nt = (unsigned long long)(n_cols / GS_TILE);
-    return na_error(NA_ERR_VERIFY,
-                    "gemm sweep: %llu of %llu waves wrong on %llu CU(s), first wave %llu (tile "
-                    "%llu,%llu sub-tile %llu,%llu) on xcc%u.se%u.sh%u.cu%u.simd%u",
-                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
-                    (unsigned long long)res->bad_units, w, t / nt, t % nt, w >> 1 & 1, w & 1, u[0],
-                    u[1], u[2], u[3], u[4]);
+    return gs_verdict("gemm sweep", recs, n, n_cols, want, res);
 }
 
 // Whole sweep on operands the agent allocates and fills itself: one untimed
@@ -2836,19 +2874,12 @@ extern "C" int na_gemm_sweep(int dev, int dtype, long long m, long long n_cols, 
                          GS_SHAPE_ARGS(m, n_cols, k, reps, gs_bk(dtype)));
     HIP_CHECK(hipSetDevice(dev));
     const size_t esize = dtype == MS_FP8 ? 1 : 2;
-    const size_t a_bytes = (size_t)(m * k) * esize, b_bytes = (size_t)(n_cols * k) * esize;
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    dev_buf<unsigned char> a, b;
-    if (a_bytes + b_bytes > free_b / 2 || a.alloc(a_bytes) != hipSuccess ||
-        b.alloc(b_bytes) != hipSuccess) {
-        (void)hipGetLastError();  // consumed here, not by a later check
-        return arg_error("na_gemm_sweep: the operands of %zu bytes (%lld x %lld and %lld x %lld) "
-                         "do not fit: %zu bytes of device memory are free and the sweep takes at "
-                         "most half",
-                         a_bytes + b_bytes, m, k, n_cols, k, free_b);
-    }
-    int rc = na_gemm_sweep_fill(dev, dtype, a.p, b.p, m, n_cols, k, seed);
+    const size_t sizes[2] = {(size_t)(m * k) * esize, (size_t)(n_cols * k) * esize};
+    dev_buf<unsigned char> bufs[2];
+    int rc = gs_alloc("na_gemm_sweep", bufs, sizes, 2, m, n_cols, k);
+    if (rc != NA_OK) return rc;
+    dev_buf<unsigned char>&a = bufs[0], &b = bufs[1];
+    rc = na_gemm_sweep_fill(dev, dtype, a.p, b.p, m, n_cols, k, seed);
     if (rc != NA_OK) return rc;
     std::vector<na_mfma_record> recs((size_t)gs_records(m, n_cols));
     double ms = 0.0;
@@ -2860,4 +2891,199 @@ extern "C" int na_gemm_sweep(int dev, int dtype, long long m, long long n_cols, 
     if (tflops) *tflops = 2.0 * (double)m * (double)n_cols * (double)k * reps / (ms * 1e9);
     return na_gemm_sweep_verify(recs.data(), (long long)recs.size(), m, n_cols, k, reps, seed,
                                 res);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide block-scaled MX GEMM sweep (kernels and specification in
+// mxgemmsweep.h)
+// ---------------------------------------------------------------------------
+//
+// The GEMM sweep above on v_mfma_scale_f32_16x16x128_f8f6f4, the instruction
+// the fp8 peak, FP4 and the serving kernels are on: operands in MXFP8 (E4M3) or
+// MXFP4 (E2M1) and an E8M0 scale per 32 elements of every row, both from device
+// memory. Tiles, records, checksum, verdict and the U/V verify are the GEMM
+// sweep's; the host folds each block's scale into U and V.
+
+#include "mxgemmsweep.h"
+
+// Chosen on the MI355X so that one launch at 8192^3 takes 15-25 ms like the
+// other sweeps: 0.80 ms (fp8) and 0.40 ms (fp4) per repetition measured, so 25
+// and 50 aim at 20 ms (profiles/mxgemm_sweep_mi355x.txt); 24 * reps * 8192 <
+// 2^24 allows up to 85.
+static int xs_default_reps(int format) { return format == MX_E2M1 ? 50 : 25; }
+
+static bool xs_format_ok(int format) { return format == MX_E4M3 || format == MX_E2M1; }
+
+// bk is the format's, or the smaller of the two where no format is at hand.
+static bool xs_shape_ok(long long m, long long n, long long k, int reps, long long bk) {
+    return m >= GS_TILE && m <= NA_GEMM_MAX_DIM && m % GS_TILE == 0 && n >= GS_TILE &&
+           n <= NA_GEMM_MAX_DIM && n % GS_TILE == 0 && k >= bk && k % bk == 0 && reps >= 1 &&
+           k < NA_MXGEMM_EXACT && 24 * (long long)reps * k < NA_MXGEMM_EXACT;
+}
+
+#define XS_SHAPE_WORDS                                                                          \
+    "m and n_cols multiples of %d in %d..%d (got %lld, %lld), k a positive multiple of %lld "   \
+    "(got %lld), reps >= 1 and 24 * reps * k < 2^24 (reps %d)"
+
+static void xs_expected(uint64_t base, long long m, long long n, long long k, int reps,
+                        uint64_t* out) {
+    const xs_bases at = xs_layout(base, (uint64_t)m, (uint64_t)n, (uint64_t)k);
+    const long long s = k / 32;
+    gs_expected_of(
+        at.p, m, n, k, reps,
+        [&](long long i, long long kk) {
+            return gs_element(at.a + (uint64_t)(i * k + kk), GS_MOD_A) *
+                   (1 << xs_exponent(at.ea + (uint64_t)(i * s + kk / 32)));
+        },
+        [&](long long j, long long kk) {
+            return gs_element(at.b + (uint64_t)(j * k + kk), GS_MOD_B) *
+                   (1 << xs_exponent(at.eb + (uint64_t)(j * s + kk / 32)));
+        },
+        out);
+}
+
+// Pure host code: all 4 * (m/256) * (n_cols/256) checksums, n_out exactly
+// that; the same for both formats.
+extern "C" int na_mxgemm_sweep_expected(unsigned long long seed, long long m, long long n_cols,
+                                        long long k, int reps, uint64_t* checksums,
+                                        long long n_out) {
+    if (!xs_shape_ok(m, n_cols, k, reps, NA_MXGEMM_BK_FP8) || checksums == nullptr ||
+        n_out != gs_records(m, n_cols))
+        return arg_error("na_mxgemm_sweep_expected: need " XS_SHAPE_WORDS
+                         " and room for exactly 4 checksums per tile (checksums %p, n_out %lld)",
+                         GS_SHAPE_ARGS(m, n_cols, k, reps, NA_MXGEMM_BK_FP8), (void*)checksums,
+                         n_out);
+    xs_expected(seed * MS_G, m, n_cols, k, reps, checksums);
+    return NA_OK;
+}
+
+// What the entry points that touch operands check, ahead of any HIP call.
+static int xs_operand_args(const char* fn, int format, const void* a, const void* b,
+                           const void* sa, const void* sb, long long m, long long n, long long k,
+                           int reps) {
+    if (!xs_format_ok(format))
+        return arg_error("%s: need format %d (fp8) or %d (fp4) (got %d)", fn, MX_E4M3, MX_E2M1,
+                         format);
+    if (!xs_shape_ok(m, n, k, reps, xs_bk(format)))
+        return arg_error("%s: need " XS_SHAPE_WORDS, fn,
+                         GS_SHAPE_ARGS(m, n, k, reps, xs_bk(format)));
+    if (a == nullptr || b == nullptr || sa == nullptr || sb == nullptr ||
+        (((uintptr_t)a | (uintptr_t)b | (uintptr_t)sa | (uintptr_t)sb) & 15) != 0)
+        return arg_error("%s: need 16-byte aligned operands and scales (a %p, b %p, sa %p, sb %p)",
+                         fn, a, b, sa, sb);
+    return NA_OK;
+}
+
+// Writes A (m x k) and B (n_cols x k) of `seed` in `format`, K-contiguous, and
+// their scales (m x k/32 and n_cols x k/32 E8M0 bytes) into caller-owned
+// device memory.
+extern "C" int na_mxgemm_sweep_fill(int dev, int format, void* a, void* b, void* sa, void* sb,
+                                    long long m, long long n_cols, long long k,
+                                    unsigned long long seed) {
+    int rc = xs_operand_args("na_mxgemm_sweep_fill", format, a, b, sa, sb, m, n_cols, k, 1);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t per_vec = 128 / mx_bits(format);
+    const uint64_t a_vecs = (uint64_t)(m * k) / per_vec, b_vecs = (uint64_t)(n_cols * k) / per_vec;
+    const uint64_t a_blocks = (uint64_t)(m * k) / 32, b_blocks = (uint64_t)(n_cols * k) / 32;
+    const xs_bases at = xs_layout(seed * MS_G, (uint64_t)m, (uint64_t)n_cols, (uint64_t)k);
+    const unsigned grid =
+        (unsigned)((a_vecs + b_vecs + a_blocks + b_blocks + MS_BLOCK - 1) / MS_BLOCK);
+    (format == MX_E2M1 ? mxgemm_fill_kernel<MX_E2M1>
+                       : mxgemm_fill_kernel<MX_E4M3>)<<<dim3(grid), dim3(MS_BLOCK)>>>(
+        static_cast<mt_vec*>(a), static_cast<mt_vec*>(b), static_cast<unsigned char*>(sa),
+        static_cast<unsigned char*>(sb), a_vecs, b_vecs, a_blocks, b_blocks, at.a, at.ea);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// One launch of one workgroup per 256 x 256 tile on caller-owned operands and
+// scales (na_mxgemm_sweep_fill of the same seed, format and shape), HIP-event
+// timed; out and c as na_gemm_sweep_run's. Argument errors are detected before
+// any HIP call.
+extern "C" int na_mxgemm_sweep_run(int dev, int format, const void* a, const void* b,
+                                   const void* sa, const void* sb, void* c, long long m,
+                                   long long n_cols, long long k, int reps,
+                                   unsigned long long seed, na_mfma_record* out, long long n_out,
+                                   double* ms) {
+    int rc = xs_operand_args("na_mxgemm_sweep_run", format, a, b, sa, sb, m, n_cols, k, reps);
+    if (rc != NA_OK) return rc;
+    if (out == nullptr || n_out != gs_records(m, n_cols) || ((uintptr_t)c & 3) != 0)
+        return arg_error("na_mxgemm_sweep_run: need room for exactly 4 records per tile (out %p, "
+                         "n_out %lld, want %lld) and c null or 4-byte aligned (%p)",
+                         (void*)out, n_out, gs_records(m, n_cols), c);
+    size_t lds_bytes = 0;
+    rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes < XS_LDS_BYTES)
+        return arg_error("na_mxgemm_sweep_run: the device's %zu-byte per-workgroup LDS allocation "
+                         "is under the %d bytes of the two stages",
+                         lds_bytes, XS_LDS_BYTES);
+    const uint32_t mt = (uint32_t)(m / GS_TILE), nt = (uint32_t)(n_cols / GS_TILE);
+    const xs_bases at = xs_layout(seed * MS_G, (uint64_t)m, (uint64_t)n_cols, (uint64_t)k);
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        (format == MX_E2M1 ? mxgemm_sweep_kernel<MX_E2M1>
+                           : mxgemm_sweep_kernel<MX_E4M3>)<<<dim3(mt * nt), dim3(MS_BLOCK),
+                                                             XS_LDS_BYTES>>>(
+            records, static_cast<const mt_vec*>(a), static_cast<const mt_vec*>(b),
+            static_cast<const uint32_t*>(sa), static_cast<const uint32_t*>(sb),
+            static_cast<float*>(c), mt, nt, (uint32_t)(k / xs_bk(format)), (uint32_t)reps, at.p);
+    });
+}
+
+// Pure host code, as na_gemm_sweep_verify.
+extern "C" int na_mxgemm_sweep_verify(const na_mfma_record* recs, long long n, long long m,
+                                      long long n_cols, long long k, int reps,
+                                      unsigned long long seed, na_mfma_sweep_result* res) {
+    if (!xs_shape_ok(m, n_cols, k, reps, NA_MXGEMM_BK_FP8) || recs == nullptr ||
+        n != gs_records(m, n_cols) || res == nullptr)
+        return arg_error("na_mxgemm_sweep_verify: need " XS_SHAPE_WORDS
+                         ", exactly 4 records per tile (recs %p, n %lld) and a result pointer",
+                         GS_SHAPE_ARGS(m, n_cols, k, reps, NA_MXGEMM_BK_FP8), (const void*)recs,
+                         n);
+    std::vector<uint64_t> want((size_t)n);
+    xs_expected(seed * MS_G, m, n_cols, k, reps, want.data());
+    return gs_verdict("mxgemm sweep", recs, n, n_cols, want, res);
+}
+
+// Whole sweep on operands and scales the agent allocates and fills itself, as
+// na_gemm_sweep: warm-up launch, timed launch, verify; 0 = default for m,
+// n_cols, k (8192 each) and reps. *tflops counts 2 * m * n_cols * k * reps FLOP
+// over the event time.
+extern "C" int na_mxgemm_sweep(int dev, int format, long long m, long long n_cols, long long k,
+                               int reps, unsigned long long seed, na_mfma_sweep_result* res,
+                               double* tflops) {
+    if (!xs_format_ok(format) || res == nullptr || m < 0 || n_cols < 0 || k < 0 || reps < 0)
+        return arg_error("na_mxgemm_sweep: need format %d (fp8) or %d (fp4) (got %d), m, n_cols, k "
+                         "and reps >= 0 (got %lld, %lld, %lld, %d) and a result pointer",
+                         MX_E4M3, MX_E2M1, format, m, n_cols, k, reps);
+    if (m == 0) m = NA_GEMM_DEFAULT_DIM;
+    if (n_cols == 0) n_cols = NA_GEMM_DEFAULT_DIM;
+    if (k == 0) k = NA_GEMM_DEFAULT_DIM;
+    if (reps == 0) reps = xs_default_reps(format);
+    if (!xs_shape_ok(m, n_cols, k, reps, xs_bk(format)))
+        return arg_error("na_mxgemm_sweep: need " XS_SHAPE_WORDS,
+                         GS_SHAPE_ARGS(m, n_cols, k, reps, xs_bk(format)));
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t bits = (size_t)mx_bits(format);
+    const size_t sizes[4] = {(size_t)(m * k) * bits / 8, (size_t)(n_cols * k) * bits / 8,
+                             (size_t)(m * k) / 32, (size_t)(n_cols * k) / 32};
+    dev_buf<unsigned char> bufs[4];
+    int rc = gs_alloc("na_mxgemm_sweep", bufs, sizes, 4, m, n_cols, k);
+    if (rc != NA_OK) return rc;
+    unsigned char *const a = bufs[0].p, *const b = bufs[1].p, *const sa = bufs[2].p,
+                         *const sb = bufs[3].p;
+    rc = na_mxgemm_sweep_fill(dev, format, a, b, sa, sb, m, n_cols, k, seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs((size_t)gs_records(m, n_cols));
+    double ms = 0.0;
+    rc = sweep_twice([&] {
+        return na_mxgemm_sweep_run(dev, format, a, b, sa, sb, nullptr, m, n_cols, k, reps, seed,
+                                   recs.data(), (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
+    if (tflops) *tflops = 2.0 * (double)m * (double)n_cols * (double)k * reps / (ms * 1e9);
+    return na_mxgemm_sweep_verify(recs.data(), (long long)recs.size(), m, n_cols, k, reps, seed,
+                                  res);
 }

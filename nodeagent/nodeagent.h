@@ -45,6 +45,9 @@
 #define NA_GEMM_BK_BF16 64       // its K is a multiple of this for bf16,
 #define NA_GEMM_BK_FP8 128       // of this for fp8 (128 bytes per row either way),
 #define NA_GEMM_EXACT (1 << 24)  // and 6 * reps * K stays under this: exact f32 integers
+#define NA_MXGEMM_BK_FP8 128     // the MX GEMM sweep's K is a multiple of this for fp8,
+#define NA_MXGEMM_BK_FP4 256     // of this for fp4 (128 bytes per row either way),
+#define NA_MXGEMM_EXACT (1 << 24)  // and 24 * reps * K stays under this: exact f32 integers
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -57,7 +60,7 @@
 // around the stream loop, for each of its stream waves; a wave of a role that
 // is switched off leaves it all zero. The GEMM sweep (gemmsweep.h) leaves it
 // for each wave of each C tile, `wave` being 4 * tile + 2 * wr + wc and the
-// clocks around the K loops.
+// clocks around the K loops, and the MX GEMM sweep (mxgemmsweep.h) the same.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -301,6 +304,25 @@ int na_gemm_sweep_verify(const na_mfma_record* recs, long long n, long long m, l
                          na_mfma_sweep_result* res);
 int na_gemm_sweep(int dev, int dtype, long long m, long long n_cols, long long k, int reps,
                   unsigned long long seed, na_mfma_sweep_result* res, double* tflops);
+
+// chip-wide block-scaled MX GEMM sweep, C = reps * (2^ea a) * (2^eb b)^T on
+// v_mfma_scale_f32_16x16x128_f8f6f4: format 0 = fp8 (MX_E4M3, a byte per
+// element), 4 = fp4 (MX_E2M1, two per byte, even k in the low nibble); a is m x
+// k, b n_cols x k, K-contiguous, sa and sb their E8M0 scales, uint8[rows][k/32];
+// shapes, records and results as the GEMM sweep's
+int na_mxgemm_sweep_fill(int dev, int format, void* a, void* b, void* sa, void* sb, long long m,
+                         long long n_cols, long long k, unsigned long long seed);
+int na_mxgemm_sweep_expected(unsigned long long seed, long long m, long long n_cols, long long k,
+                             int reps, uint64_t* checksums, long long n_out);
+int na_mxgemm_sweep_run(int dev, int format, const void* a, const void* b, const void* sa,
+                        const void* sb, void* c, long long m, long long n_cols, long long k,
+                        int reps, unsigned long long seed, na_mfma_record* out, long long n_out,
+                        double* ms);
+int na_mxgemm_sweep_verify(const na_mfma_record* recs, long long n, long long m, long long n_cols,
+                           long long k, int reps, unsigned long long seed,
+                           na_mfma_sweep_result* res);
+int na_mxgemm_sweep(int dev, int format, long long m, long long n_cols, long long k, int reps,
+                    unsigned long long seed, na_mfma_sweep_result* res, double* tflops);
 
 #ifdef __cplusplus
 }
