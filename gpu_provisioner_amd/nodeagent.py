@@ -7,7 +7,8 @@ there is no eager/python fallback for the hardware checks.
 
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
-[--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]``
+[--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]
+[--mxquant-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -205,6 +206,24 @@ MXGEMM_SWEEP_BK = {"fp8": 128, "fp4": 256}  # k is a multiple of this
 # device-to-device spread has not been measured; 0.70 is borrowed from the MFMA
 # floor. 0 disables a floor.
 MIN_MXGEMM_SWEEP_TFLOPS = {"fp8": 1046.9, "fp4": 2312.2}
+
+# Chip-wide MX quantise sweep (nodeagent/mxquantsweep.h): the OCP MX quantiser
+# that produces the MX GEMM's operands in service, bf16 to MXFP8 / MXFP6 / MXFP4
+# and an E8M0 scale per 32 elements, on the gfx950 scaled conversion
+# instructions; also an operation on caller-owned tensors (``mxquant_run``).
+# The default seed is "MI355XQS"; records and results are the matrix-core
+# sweep's, record 4 * workgroup + wave. The format codes are MX_E4M3, MX_E2M3
+# and MX_E2M1 of nodeagent/mx_formats.h.
+DEFAULT_MXQUANT_SWEEP_SEED = 0x4D493335_35585153
+MXQUANT_FORMATS = {"fp8": 0, "fp6": 2, "fp4": 4}
+MXQUANT_BITS = {"fp8": 8, "fp6": 6, "fp4": 4}  # a block of 32 is 4 x this many bytes
+# Floors of the default sweep's conversion rate per format, in 10^9 elements
+# per second from the in-kernel clocks (not a memory figure: the slices are
+# served from cache): 0.70 x the 2544.2, 2882.4 and 3028.4 Gelem/s medians of
+# five processes on MI355X (profiles/mxquant_sweep_mi355x.txt), the rule of the
+# floors above. The device-to-device spread of conversion loops has not been
+# measured; 0.70 is borrowed from the MFMA floor. 0 disables a floor.
+MIN_MXQUANT_SWEEP_GELEMS = {"fp8": 1780.9, "fp6": 2017.7, "fp4": 2119.9}
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -415,6 +434,29 @@ class GemmSweepResult:
         return (
             f"{self.sweep.describe()}; first wave {w} on {mfma_unit_name(self.sweep.bad_simds[0])}"
             f" computed tile ({tile // nt},{tile % nt}) sub-tile ({w >> 1 & 1},{w & 1})"
+        )
+
+
+@dataclass
+class MxQuantSweepResult:
+    """Outcome of an MX quantise sweep verify: the matrix-core sweep's result
+    over the 4 waves of every workgroup, and the conversion rate of the timed
+    launch in 10^9 elements per second, from the in-kernel clocks (0 when only
+    a verify was done). It is not a memory figure."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    gelems: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong wave by workgroup and unit."""
+        w = self.sweep.first_bad_wave
+        return (
+            f"{self.sweep.describe()}; first wave {w} (workgroup {w // 4} wave {w % 4}) on "
+            f"{mfma_unit_name(self.sweep.bad_simds[0])}"
         )
 
 
@@ -771,6 +813,16 @@ _ABI = {
         _int, (_P(MfmaRecord), _i64, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC))),
     "na_mxgemm_sweep": (
         _int, (_int, _int, _i64, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
+    "na_mxquant_reference": (_int, (_int, _void_p, _i64, _i64, _void_p, _void_p)),
+    "na_mxquant_fill": (_int, (_int, _void_p, _i64, _i64, _u64)),
+    "na_mxquant_expected": (_int, (_int, _u64, _i64, _i64, _int, _int, _u64_p, _i64)),
+    "na_mxquant_run": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _i64, _i64, _int, _int, _u64,
+               _P(MfmaRecord), _i64, _double_p)),
+    "na_mxquant_verify": (
+        _int, (_P(MfmaRecord), _i64, _int, _i64, _i64, _int, _int, _u64, _P(_MfmaSweepResultC))),
+    "na_mxquant_sweep": (
+        _int, (_int, _int, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
 }
 
 
@@ -843,6 +895,13 @@ class GPUReport:
     mxgemm_sweep_units_seen: int = 0
     mxgemm_sweep_bad_waves: int = 0  # of both formats
     mxgemm_sweep_skipped: str = ""  # reason, when requested but not run
+    # chip-wide MX quantise sweep (opt-in; all "not run" by default)
+    mxquant_sweep_fp8_gelems: float = 0.0  # conversion rates, not memory figures
+    mxquant_sweep_fp6_gelems: float = 0.0
+    mxquant_sweep_fp4_gelems: float = 0.0
+    mxquant_sweep_clock_mhz: float = 0.0  # fp8 run; informational, no floor
+    mxquant_sweep_units_seen: int = 0
+    mxquant_sweep_bad_waves: int = 0  # of the three formats
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -1787,6 +1846,105 @@ class NodeAgent:
             if not res.ok:
                 g.problems.append(f"MX GEMM sweep {fmt}: {res.describe()}")
 
+    # -- chip-wide MX quantise sweep ----------------------------------------------
+
+    @staticmethod
+    def _mxquant_code(fmt: str) -> int:
+        if fmt not in MXQUANT_FORMATS:
+            raise NodeAgentError(
+                f"mxquant: format {fmt!r} is not one of {', '.join(MXQUANT_FORMATS)}")
+        return MXQUANT_FORMATS[fmt]
+
+    def mxquant_reference(self, src, rows: int, k: int, fmt: str = "fp8") -> tuple:
+        """The GPU-free OCP MX quantiser: ``src`` (``rows`` x ``k`` bf16 as a
+        bytes-like object of ``2 * rows * k`` bytes) into ``(dst, scales)``,
+        two ``bytes``: the packed elements in ``fmt`` and the E8M0 scale of
+        every 32 elements. Host arithmetic only; makes no HIP call."""
+        code, blocks = self._mxquant_code(fmt), max(rows * k // 32, 1)
+        if len(src) < 2 * rows * k:
+            raise NodeAgentError(f"mxquant_reference: src holds {len(src)} bytes, not {2 * rows * k}")
+        buf = (ctypes.c_char * len(src)).from_buffer_copy(src)
+        dst = (ctypes.c_char * (blocks * 4 * MXQUANT_BITS[fmt]))()
+        scales = (ctypes.c_char * blocks)()
+        rc = self.lib.na_mxquant_reference(code, buf, rows, k, dst, scales)
+        self._check(rc, "mxquant_reference")
+        return dst.raw, scales.raw
+
+    def mxquant_fill(self, dev: int, src: int, rows: int, k: int,
+                     seed: int = DEFAULT_MXQUANT_SWEEP_SEED) -> None:
+        """Write the sweep's hashed source (``rows`` x ``k`` bf16: block
+        binades over +-20, eleven binades within a block, zeros, ties and
+        saturating values) into the caller-owned device memory at ``src``."""
+        self._check(self.lib.na_mxquant_fill(dev, src, rows, k, seed), f"mxquant_fill({dev})")
+
+    def mxquant_expected(self, rows: int, k: int, workgroups: int, passes: int = 1,
+                         seed: int = DEFAULT_MXQUANT_SWEEP_SEED, fmt: str = "fp8") -> list:
+        """The checksums of all ``4 * workgroups`` waves of a run on
+        ``mxquant_fill``'s source. Host arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * max(4 * workgroups, 1))()
+        rc = self.lib.na_mxquant_expected(self._mxquant_code(fmt), seed, rows, k, workgroups,
+                                          passes, out, len(out))
+        self._check(rc, "mxquant_expected")
+        return list(out)
+
+    def mxquant_run(self, dev: int, src: int, dst: int, scales: int, rows: int, k: int,
+                    workgroups: int, passes: int = 1, seed: int = DEFAULT_MXQUANT_SWEEP_SEED,
+                    fmt: str = "fp8") -> tuple:
+        """One launch of ``workgroups`` x 4 waves that quantises the ``rows`` x
+        ``k`` bf16 tensor at ``src`` into ``dst`` (``rows * k * bits / 8``
+        bytes) and ``scales`` (``rows * k / 32`` bytes), all caller-owned device
+        memory, ``passes`` times over. Any tensor inside the contract (finite,
+        no bf16 subnormals) can be quantised; ``seed`` only weighs the
+        checksums. Returns ``(records, ms)``."""
+        recs = (MfmaRecord * max(4 * workgroups, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_mxquant_run(dev, self._mxquant_code(fmt), src, dst, scales, rows, k,
+                                     workgroups, passes, seed, recs, len(recs), ctypes.byref(ms))
+        self._check(rc, f"mxquant_run({dev})")
+        return recs, ms.value
+
+    def mxquant_verify(self, recs, rows: int, k: int, workgroups: int, passes: int = 1,
+                       seed: int = DEFAULT_MXQUANT_SWEEP_SEED, fmt: str = "fp8") -> tuple:
+        """Compare every record's checksum against the host's own quantiser on
+        ``mxquant_fill``'s source of ``seed``. Returns ``(rc,
+        MxQuantSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad wave."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_mxquant_verify(recs, len(recs), self._mxquant_code(fmt), rows, k,
+                                        workgroups, passes, seed, ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, MxQuantSweepResult()
+        return rc, MxQuantSweepResult(MfmaSweepResult._from_c(fmt, res))
+
+    def mxquant_sweep(self, dev: int, fmt: str = "fp8", workgroups: int = 0, passes: int = 0,
+                      seed: int = DEFAULT_MXQUANT_SWEEP_SEED) -> MxQuantSweepResult:
+        """Allocate and fill a source of four tiles per workgroup, quantise it
+        twice (the second launch timed) and verify every wave bit-exactly (0 =
+        the default: 4 workgroups per CU and the format's ``passes`` of a
+        15-20 ms launch). Wrong waves come back in the result (``.ok`` False),
+        not as an exception. ``gelems`` is a conversion rate from the in-kernel
+        clocks on cache-resident slices, not a memory figure."""
+        res, gelems = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_mxquant_sweep(dev, self._mxquant_code(fmt), workgroups, passes, seed,
+                                       ctypes.byref(res), ctypes.byref(gelems))
+        self._check(rc, f"mxquant_sweep({dev}, {fmt})", ok=(NA_OK, NA_ERR_VERIFY))
+        return MxQuantSweepResult(MfmaSweepResult._from_c(fmt, res), gelems.value)
+
+    def _run_mxquant_sweep(self, g: GPUReport) -> None:
+        for fmt in MXQUANT_FORMATS:
+            res = self.mxquant_sweep(g.index, fmt)
+            setattr(g, f"mxquant_sweep_{fmt}_gelems", round(res.gelems, 1))
+            g.mxquant_sweep_bad_waves += res.sweep.bad_waves
+            if fmt == "fp8":
+                g.mxquant_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+                g.mxquant_sweep_units_seen = res.sweep.units_seen
+            if res.gelems < MIN_MXQUANT_SWEEP_GELEMS[fmt]:
+                g.problems.append(
+                    f"MX quantise sweep {fmt} {round(res.gelems, 1)} Gelem/s (conversion rate) "
+                    f"below floor {MIN_MXQUANT_SWEEP_GELEMS[fmt]}"
+                )
+            if not res.ok:
+                g.problems.append(f"MX quantise sweep {fmt}: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -1805,7 +1963,7 @@ class NodeAgent:
               mx_sweep: bool = False, lds_sweep: bool = False,
               valu_sweep: bool = False, cache_sweep: bool = False,
               load_sweep: bool = False, gemm_sweep: bool = False,
-              mxgemm_sweep: bool = False) -> NodeReport:
+              mxgemm_sweep: bool = False, mxquant_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -1873,7 +2031,16 @@ class NodeAgent:
         memory like the operands. A wrong wave is a problem that names its
         format, unit, tile and sub-tile, as is a rate under the format's
         ``MIN_MXGEMM_SWEEP_TFLOPS``; operands that do not fit land in
-        ``mxgemm_sweep_skipped``. False (default) makes no new library call."""
+        ``mxgemm_sweep_skipped``. False (default) makes no new library call.
+
+        ``mxquant_sweep`` additionally runs the chip-wide MX quantise sweep on
+        every GPU: the bf16 to MXFP8 / MXFP6 / MXFP4 quantiser that produces
+        those operands in service, on the scaled conversion instructions,
+        every wave's packed elements and scale bytes checked against the
+        host's own quantiser. A wrong wave is a problem that names its format,
+        workgroup and unit, as is a conversion rate under the format's
+        ``MIN_MXQUANT_SWEEP_GELEMS``. False (default) makes no new library
+        call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -1925,6 +2092,8 @@ class NodeAgent:
                     self._run_gemm_sweep(g)
                 if mxgemm_sweep:
                     self._run_mxgemm_sweep(g)
+                if mxquant_sweep:
+                    self._run_mxquant_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -2098,6 +2267,16 @@ def main(argv=None) -> int:
         "is attributed to its XCC/SE/SH/CU/SIMD, tile and sub-tile; reports the rate per format",
     )
     ap.add_argument(
+        "--mxquant-sweep",
+        action="store_true",
+        help="also run the chip-wide MX quantise sweep on every GPU: the OCP MX quantiser (bf16 "
+        "in; per 32 elements the largest magnitude, an E8M0 scale and the elements through the "
+        "scaled conversion instructions; MXFP8, MXFP6 and MXFP4 out) on one wave per SIMD of "
+        "every CU, every wave's output checked against the host's own quantiser and a wrong one "
+        "attributed to its XCC/SE/SH/CU/SIMD; reports a conversion rate per format from the "
+        "in-kernel clocks (cache-resident slices: not a memory figure)",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -2119,6 +2298,7 @@ def main(argv=None) -> int:
             load_sweep=args.load_sweep,
             gemm_sweep=args.gemm_sweep,
             mxgemm_sweep=args.mxgemm_sweep,
+            mxquant_sweep=args.mxquant_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

@@ -26,7 +26,10 @@
 // multiply from device memory through L2 and LDS into the MFMA, every wave's
 // share of C checked, gemmsweep.h), the same on the block-scaled instruction
 // in MXFP8 and MXFP4 with E8M0 scales that come from device memory too
-// (mxgemmsweep.h), and the xGMI peer-to-peer link matrix. The
+// (mxgemmsweep.h), an opt-in chip-wide MX quantise sweep (the bf16 to
+// MXFP8/FP6/FP4 quantiser that produces those operands in service, on the
+// scaled conversion instructions, also callable on caller-owned tensors,
+// mxquantsweep.h), and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
 // sweeps" below): a further sweep starts from those.
@@ -3086,4 +3089,248 @@ extern "C" int na_mxgemm_sweep(int dev, int format, long long m, long long n_col
     if (tflops) *tflops = 2.0 * (double)m * (double)n_cols * (double)k * reps / (ms * 1e9);
     return na_mxgemm_sweep_verify(recs.data(), (long long)recs.size(), m, n_cols, k, reps, seed,
                                   res);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide MX quantise sweep (kernels and specification in mxquantsweep.h)
+// ---------------------------------------------------------------------------
+//
+// What produces the MX GEMM's operands in service: bf16 in, per 32 elements the
+// largest magnitude, its E8M0 scale and the elements through the gfx950 scaled
+// conversion instructions, packed elements and scale bytes out. As a sweep on
+// a hashed source, every wave's output folded into a checksum the host
+// recomputes with its own quantiser (qs_reference_block), and as an operation
+// on caller-owned tensors (na_mxquant_run takes any source; its seed only
+// weighs the checksum).
+
+#include "mxquantsweep.h"
+
+// The whole sweep's shape: rows of one tile (256 blocks of 32), and so many
+// tiles for every workgroup that the two LDS stages and the wrap to the first
+// tile are all in use. The source of the default grid is 64 MiB.
+#define QS_SWEEP_K (QS_TILE * NA_MXQUANT_BLOCK)
+#define QS_SWEEP_TILES_PER_WG 4
+#define QS_SWEEP_MAX_WORKGROUPS (NA_MXQUANT_MAX_BLOCKS / (QS_TILE * QS_SWEEP_TILES_PER_WG))
+// Chosen on the MI355X so that one launch of the default grid takes 15-20 ms
+// like the other sweeps: 14.4 us (fp8), 12.4 us (fp6) and 11.6 us (fp4) per
+// pass measured, so these aim at 17 ms (profiles/mxquant_sweep_mi355x.txt).
+static int qs_default_passes(int format) {
+    return format == MX_E4M3 ? 1200 : format == MX_E2M3 ? 1400 : 1500;
+}
+
+static const char* qs_name(int format) {
+    return format == MX_E4M3 ? "fp8" : format == MX_E2M3 ? "fp6" : "fp4";
+}
+
+// What every entry point checks of the shape, ahead of any HIP call.
+// workgroups and passes: 1 where the caller has none.
+static int qs_shape_args(const char* fn, int format, long long rows, long long k, int workgroups,
+                         int passes) {
+    if (!qs_format_ok(format))
+        return arg_error("%s: need format %d (fp8), %d (fp6) or %d (fp4) (got %d)", fn, MX_E4M3,
+                         MX_E2M3, MX_E2M1, format);
+    if (rows < 1 || rows > NA_MXQUANT_MAX_BLOCKS || k < NA_MXQUANT_BLOCK ||
+        k % NA_MXQUANT_BLOCK != 0 || k / NA_MXQUANT_BLOCK > NA_MXQUANT_MAX_BLOCKS ||
+        rows * (k / NA_MXQUANT_BLOCK) > NA_MXQUANT_MAX_BLOCKS)
+        return arg_error("%s: need rows >= 1 (got %lld), k a positive multiple of %d (got %lld) "
+                         "and at most %d blocks of %d elements",
+                         fn, rows, NA_MXQUANT_BLOCK, k, NA_MXQUANT_MAX_BLOCKS, NA_MXQUANT_BLOCK);
+    if (workgroups < 1 || workgroups > NA_MFMA_MAX_WORKGROUPS || passes < 1 ||
+        passes > NA_MXQUANT_MAX_PASSES)
+        return arg_error("%s: need workgroups in 1..%d (got %d) and passes in 1..%d (got %d)", fn,
+                         NA_MFMA_MAX_WORKGROUPS, workgroups, NA_MXQUANT_MAX_PASSES, passes);
+    return NA_OK;
+}
+
+// The GPU-free quantiser: src (rows x k bf16) into dst and scales, all host
+// memory, by the rules at the top of mxquantsweep.h. No HIP call.
+extern "C" int na_mxquant_reference(int format, const void* src, long long rows, long long k,
+                                    void* dst, void* scales) {
+    int rc = qs_shape_args("na_mxquant_reference", format, rows, k, 1, 1);
+    if (rc != NA_OK) return rc;
+    if (src == nullptr || dst == nullptr || scales == nullptr)
+        return arg_error("na_mxquant_reference: need src, dst and scales (got %p, %p, %p)", src,
+                         dst, scales);
+    const size_t blocks = (size_t)(rows * (k / NA_MXQUANT_BLOCK)), bytes = 4 * mx_bits(format);
+    uint32_t words[8];
+    for (size_t x = 0; x < blocks; ++x) {
+        uint16_t in[32];
+        std::memcpy(in, static_cast<const unsigned char*>(src) + 64 * x, sizeof(in));
+        static_cast<unsigned char*>(scales)[x] =
+            (unsigned char)qs_reference_block(format, in, words);
+        std::memcpy(static_cast<unsigned char*>(dst) + bytes * x, words, bytes);
+    }
+    return NA_OK;
+}
+
+// The checksums of a run on the source of `base`: out[4 * g + v] for wave v
+// of workgroup g of `workgroups`.
+static void qs_expected(int format, uint64_t base, uint64_t blocks, uint64_t workgroups,
+                        uint64_t passes, uint64_t* out) {
+    std::fill(out, out + workgroups * MS_WAVES_PER_WG, (uint64_t)0);
+    uint32_t words[8];
+    for (uint64_t x = 0; x < blocks; ++x) {
+        uint16_t in[32];
+        const int binade = qs_binade(base, blocks * 32, x);
+        for (int i = 0; i < 32; ++i) in[i] = (uint16_t)qs_element(base, x * 32 + i, binade);
+        uint32_t h = qs_reference_block(format, in, words);
+        for (int i = 0; i < mx_bits(format); ++i) h = qs_fold(h, words[i]);
+        out[x / QS_TILE % workgroups * MS_WAVES_PER_WG + x % QS_TILE / 64] +=
+            passes * qs_weight(base, x) * h;
+    }
+}
+
+// Pure host code: the checksums of na_mxquant_run on the source na_mxquant_fill
+// writes for `seed`, n_out at least 4 * workgroups.
+extern "C" int na_mxquant_expected(int format, unsigned long long seed, long long rows,
+                                   long long k, int workgroups, int passes, uint64_t* checksums,
+                                   long long n_out) {
+    int rc = qs_shape_args("na_mxquant_expected", format, rows, k, workgroups, passes);
+    if (rc != NA_OK) return rc;
+    if (checksums == nullptr || n_out < (long long)workgroups * MS_WAVES_PER_WG)
+        return arg_error("na_mxquant_expected: need room for 4 checksums per workgroup (checksums "
+                         "%p, n_out %lld)",
+                         (void*)checksums, n_out);
+    qs_expected(format, seed * MS_G, (uint64_t)(rows * (k / NA_MXQUANT_BLOCK)),
+                (uint64_t)workgroups, (uint64_t)passes, checksums);
+    return NA_OK;
+}
+
+// Writes the sweep's hashed source of `seed` (rows x k bf16) into caller-owned
+// device memory.
+extern "C" int na_mxquant_fill(int dev, void* src, long long rows, long long k,
+                               unsigned long long seed) {
+    int rc = qs_shape_args("na_mxquant_fill", MX_E4M3, rows, k, 1, 1);
+    if (rc != NA_OK) return rc;
+    if (src == nullptr || ((uintptr_t)src & 15) != 0)
+        return arg_error("na_mxquant_fill: need a 16-byte aligned src (got %p)", src);
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t vecs = (uint64_t)(rows * k) / 8;
+    mxquant_fill_kernel<<<dim3((unsigned)((vecs + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK)>>>(
+        static_cast<qs_vec*>(src), vecs, seed * MS_G);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// One launch of `workgroups` x 4 waves on caller-owned device memory, HIP-event
+// timed: src (rows x k bf16, any values inside the contract) quantised into
+// dst and scales, `passes` times over; records receives the 4 * workgroups
+// records. Argument errors are detected before any HIP call.
+extern "C" int na_mxquant_run(int dev, int format, const void* src, void* dst, void* scales,
+                              long long rows, long long k, int workgroups, int passes,
+                              unsigned long long seed, na_mfma_record* records, long long n_out,
+                              double* ms) {
+    int rc = qs_shape_args("na_mxquant_run", format, rows, k, workgroups, passes);
+    if (rc != NA_OK) return rc;
+    if (src == nullptr || dst == nullptr || scales == nullptr ||
+        (((uintptr_t)src | (uintptr_t)dst) & 15) != 0 || ((uintptr_t)scales & 3) != 0)
+        return arg_error("na_mxquant_run: need 16-byte aligned src and dst and 4-byte aligned "
+                         "scales (got %p, %p, %p)",
+                         src, dst, scales);
+    if (records == nullptr || n_out < (long long)workgroups * MS_WAVES_PER_WG)
+        return arg_error("na_mxquant_run: need room for 4 records per workgroup (records %p, "
+                         "n_out %lld)",
+                         (void*)records, n_out);
+    size_t lds_bytes = 0;
+    rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes < QS_LDS_BYTES)
+        return arg_error("na_mxquant_run: the device's %zu-byte per-workgroup LDS allocation is "
+                         "under the %d bytes of the stages",
+                         lds_bytes, QS_LDS_BYTES);
+    static void (*const kernels[MX_FORMATS])(na_mfma_record*, const qs_vec*, unsigned char*,
+                                             unsigned char*, uint32_t, uint32_t, mt_u64) = {
+        mxquant_sweep_kernel<MX_E4M3>, nullptr, mxquant_sweep_kernel<MX_E2M3>, nullptr,
+        mxquant_sweep_kernel<MX_E2M1>};
+    const size_t n = (size_t)workgroups * MS_WAVES_PER_WG;
+    return sweep_launch(dev, n, records, ms, [&](na_mfma_record* recs) {
+        kernels[format]<<<dim3((unsigned)workgroups), dim3(MS_BLOCK), lds_bytes>>>(
+            recs, static_cast<const qs_vec*>(src), static_cast<unsigned char*>(dst),
+            static_cast<unsigned char*>(scales), (uint32_t)(rows * (k / NA_MXQUANT_BLOCK)),
+            (uint32_t)passes, seed * MS_G);
+    });
+}
+
+// Pure host code: the records of a run on na_mxquant_fill's source of `seed`,
+// record i wave i % 4 of workgroup i / 4. Returns NA_ERR_VERIFY on any bad wave
+// (ms_tally's rules), with a message that names the first; *res is filled
+// either way.
+extern "C" int na_mxquant_verify(const na_mfma_record* recs, long long n, int format,
+                                 long long rows, long long k, int workgroups, int passes,
+                                 unsigned long long seed, na_mfma_sweep_result* res) {
+    int rc = qs_shape_args("na_mxquant_verify", format, rows, k, workgroups, passes);
+    if (rc != NA_OK) return rc;
+    if (recs == nullptr || n != (long long)workgroups * MS_WAVES_PER_WG || res == nullptr)
+        return arg_error("na_mxquant_verify: need exactly 4 records per workgroup (recs %p, n "
+                         "%lld) and a result pointer",
+                         (const void*)recs, n);
+    std::vector<uint64_t> want((size_t)n);
+    qs_expected(format, seed * MS_G, (uint64_t)(rows * (k / NA_MXQUANT_BLOCK)),
+                (uint64_t)workgroups, (uint64_t)passes, want.data());
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const unsigned long long w = res->first_bad_wave;
+    return na_error(NA_ERR_VERIFY,
+                    "mxquant sweep %s: %llu of %llu waves wrong on %llu CU(s), first wave %llu "
+                    "(workgroup %llu wave %llu) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    qs_name(format), (unsigned long long)res->bad_waves,
+                    (unsigned long long)res->waves, (unsigned long long)res->bad_units, w,
+                    w / MS_WAVES_PER_WG, w % MS_WAVES_PER_WG, u[0], u[1], u[2], u[3], u[4]);
+}
+
+// Whole sweep on memory the agent allocates and fills itself: warm-up launch,
+// timed launch, verify; 0 = default for workgroups (4 per CU) and passes (the
+// format's). The source is 4 * workgroups rows of 8192: four tiles for every
+// workgroup, 64 KiB that its passes after the first find in cache. *gelems is
+// a conversion rate from the in-kernel stamps, not a memory figure: the median
+// wave's elements per shader clock x the SIMDs seen x the median clock, in
+// 10^9 elements per second.
+extern "C" int na_mxquant_sweep(int dev, int format, int workgroups, int passes,
+                                unsigned long long seed, na_mfma_sweep_result* res,
+                                double* gelems) {
+    if (!qs_format_ok(format) || res == nullptr || workgroups < 0 ||
+        workgroups > QS_SWEEP_MAX_WORKGROUPS || passes < 0 ||
+        passes > NA_MXQUANT_MAX_PASSES)
+        return arg_error("na_mxquant_sweep: need format %d (fp8), %d (fp6) or %d (fp4) (got %d), "
+                         "workgroups in 0..%d (got %d), passes in 0..%d (got %d) and a result "
+                         "pointer",
+                         MX_E4M3, MX_E2M3, MX_E2M1, format,
+                         QS_SWEEP_MAX_WORKGROUPS, workgroups,
+                         NA_MXQUANT_MAX_PASSES, passes);
+    int rc = sweep_defaults(dev, &workgroups, &passes, qs_default_passes(format));
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipSetDevice(dev));
+    const long long rows = (long long)workgroups * QS_SWEEP_TILES_PER_WG, k = QS_SWEEP_K;
+    const size_t blocks = (size_t)rows * QS_TILE;
+    dev_buf<unsigned char> src, dst, scales;
+    HIP_CHECK(src.alloc(blocks * 64));
+    HIP_CHECK(dst.alloc(blocks * 4 * mx_bits(format)));
+    HIP_CHECK(scales.alloc(blocks));
+    rc = na_mxquant_fill(dev, src.p, rows, k, seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs((size_t)workgroups * MS_WAVES_PER_WG);
+    double ms = 0.0;
+    rc = sweep_twice([&] {
+        return na_mxquant_run(dev, format, src.p, dst.p, scales.p, rows, k, workgroups, passes,
+                              seed, recs.data(), (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
+    rc = na_mxquant_verify(recs.data(), (long long)recs.size(), format, rows, k, workgroups,
+                           passes, seed, res);
+    if (gelems) {
+        sweep_census census;
+        std::vector<uint64_t> cycles;
+        for (const na_mfma_record& r : recs) {
+            census.see(r, r.simd);
+            cycles.push_back(r.cycles);
+        }
+        const double per_wave = (double)passes * QS_SWEEP_TILES_PER_WG * 64 * NA_MXQUANT_BLOCK;
+        const uint64_t median = median_of(cycles);
+        *gelems = median == 0 ? 0.0
+                              : per_wave / (double)median * (double)census.simds_seen *
+                                    census.clock_mhz() / 1e3;
+    }
+    return rc;
 }

@@ -48,6 +48,9 @@
 #define NA_MXGEMM_BK_FP8 128     // the MX GEMM sweep's K is a multiple of this for fp8,
 #define NA_MXGEMM_BK_FP4 256     // of this for fp4 (128 bytes per row either way),
 #define NA_MXGEMM_EXACT (1 << 24)  // and 24 * reps * K stays under this: exact f32 integers
+#define NA_MXQUANT_BLOCK 32      // the MX quantiser's K is a multiple of this: elements per scale,
+#define NA_MXQUANT_MAX_BLOCKS (1 << 24)  // rows * K / 32 is at most this (1 GiB of bf16),
+#define NA_MXQUANT_MAX_PASSES (1 << 20)  // and a launch repeats its slice at most this often
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -61,6 +64,8 @@
 // is switched off leaves it all zero. The GEMM sweep (gemmsweep.h) leaves it
 // for each wave of each C tile, `wave` being 4 * tile + 2 * wr + wc and the
 // clocks around the K loops, and the MX GEMM sweep (mxgemmsweep.h) the same.
+// The MX quantise sweep (mxquantsweep.h) leaves it for each wave of each
+// workgroup, `wave` being 4 * workgroup + wave and the clocks around the passes.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -323,6 +328,27 @@ int na_mxgemm_sweep_verify(const na_mfma_record* recs, long long n, long long m,
                            na_mfma_sweep_result* res);
 int na_mxgemm_sweep(int dev, int format, long long m, long long n_cols, long long k, int reps,
                     unsigned long long seed, na_mfma_sweep_result* res, double* tflops);
+
+// chip-wide MX quantise sweep, and the OCP MX quantiser it runs as an operation
+// on caller-owned tensors: format 0 = fp8 (MX_E4M3), 2 = fp6 (MX_E2M3), 4 = fp4
+// (MX_E2M1); src is rows x k bf16, K-contiguous, k a multiple of 32; dst the
+// packed elements (fp8 a byte each, fp4 two per byte with the even k in the low
+// nibble, fp6 element i of a block at bit 6 i of its 24 bytes), scales
+// uint8[rows][k/32] of E8M0 bytes; rules, layout and checksum in mxquantsweep.h;
+// records and results are the matrix-core sweep's, record 4 * workgroup + wave
+int na_mxquant_reference(int format, const void* src, long long rows, long long k, void* dst,
+                         void* scales);
+int na_mxquant_fill(int dev, void* src, long long rows, long long k, unsigned long long seed);
+int na_mxquant_expected(int format, unsigned long long seed, long long rows, long long k,
+                        int workgroups, int passes, uint64_t* checksums, long long n_out);
+int na_mxquant_run(int dev, int format, const void* src, void* dst, void* scales, long long rows,
+                   long long k, int workgroups, int passes, unsigned long long seed,
+                   na_mfma_record* records, long long n_out, double* ms);
+int na_mxquant_verify(const na_mfma_record* recs, long long n, int format, long long rows,
+                      long long k, int workgroups, int passes, unsigned long long seed,
+                      na_mfma_sweep_result* res);
+int na_mxquant_sweep(int dev, int format, int workgroups, int passes, unsigned long long seed,
+                     na_mfma_sweep_result* res, double* gelems);
 
 #ifdef __cplusplus
 }
