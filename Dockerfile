@@ -13,8 +13,10 @@
 FROM --platform=linux/amd64 rocm/dev-ubuntu-22.04:6.4 AS builder
 WORKDIR /src
 COPY nodeagent/ nodeagent/
-RUN hipcc --offload-arch=gfx950 -O3 -shared -fPIC \
-      nodeagent/agent.hip -o /src/libmi355x_nodeagent.so
+RUN hipcc --offload-arch=gfx950 -O3 -fPIC -Xclang -target-feature -Xclang -packed-fp32-ops \
+      -c nodeagent/attnsweep.hip -o /src/attnsweep.o && \
+    hipcc --offload-arch=gfx950 -O3 -shared -fPIC \
+      /src/attnsweep.o nodeagent/agent.hip -o /src/libmi355x_nodeagent.so
 # JSON-tree, object-model and revision-store extensions: Ubuntu 22.04's python3 is 3.10, the runtime stage's
 # version, so the modules' ABI tag matches (a mismatch is not loaded and the
 # package falls back to pure Python)

@@ -25,9 +25,13 @@ build: nodeagent jsontree objmodel revstore
 
 nodeagent: gpu_provisioner_amd/_native/libmi355x_nodeagent.so
 
-gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip $(wildcard nodeagent/*.h)
+# attnsweep.hip is built with the packed-f32 VALU forms off (the file says why);
+# its object goes ahead of agent.hip, since hipcc reads what follows a .hip as HIP
+gpu_provisioner_amd/_native/libmi355x_nodeagent.so: nodeagent/agent.hip nodeagent/attnsweep.hip $(wildcard nodeagent/*.h)
 	mkdir -p gpu_provisioner_amd/_native
-	$(HIPCC) --offload-arch=$(OFFLOAD_ARCH) -O3 -shared -fPIC $< -o $@
+	$(HIPCC) --offload-arch=$(OFFLOAD_ARCH) -O3 -fPIC -Xclang -target-feature -Xclang -packed-fp32-ops \
+		-c nodeagent/attnsweep.hip -o gpu_provisioner_amd/_native/attnsweep.o
+	$(HIPCC) --offload-arch=$(OFFLOAD_ARCH) -O3 -shared -fPIC gpu_provisioner_amd/_native/attnsweep.o $< -o $@
 
 # CPython extension for the JSON-tree walks (deep copy, merge patch, CRD
 # validation verdict); the package falls back to pure Python without it

@@ -8,7 +8,7 @@ there is no eager/python fallback for the hardware checks.
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
 [--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]
-[--mxquant-sweep]``
+[--mxquant-sweep] [--attn-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -16,6 +16,7 @@ from __future__ import annotations
 import argparse
 import ctypes
 import json
+import math
 import os
 import sys
 from dataclasses import asdict, dataclass, field, fields
@@ -224,6 +225,26 @@ MXQUANT_BITS = {"fp8": 8, "fp6": 6, "fp4": 4}  # a block of 32 is 4 x this many 
 # floors above. The device-to-device spread of conversion loops has not been
 # measured; 0.70 is borrowed from the MFMA floor. 0 disables a floor.
 MIN_MXQUANT_SWEEP_GELEMS = {"fp8": 1780.9, "fp6": 2017.7, "fp4": 2119.9}
+
+# Chip-wide fused attention sweep (nodeagent/attnsweep.h): O = softmax(scale Q
+# K^T [+ causal mask]) V in bf16 with GQA at head dimension 128, two chained
+# MFMA products with an online softmax between them, on hashed integer operands
+# whose every intermediate is an exact f32; also an operation on caller-owned
+# tensors (``attn_run``). The default seed is "MI355XAT"; records and results
+# are the matrix-core sweep's, record 4 * (head * n_q / 128 + block) + wave.
+DEFAULT_ATTN_SWEEP_SEED = 0x4D493335_35584154
+# nodeagent/nodeagent.h: NA_ATTN_HEAD_DIM, NA_ATTN_Q_BLOCK, NA_ATTN_K_TILE
+ATTN_HEAD_DIM = 128
+ATTN_Q_BLOCK = 128  # n_q is a multiple of this
+ATTN_K_TILE = 64  # n_k of this
+ATTN_SWEEP_SEQ = 512  # agent.hip: NA_ATTN_DEFAULT_SEQ, the default n_q and n_k
+# Floors of the default sweep (512 heads on 128 KV heads, 512 x 512, 127
+# repetitions), full and causal: 0.70 x the 945.8 and 667.9 TFLOP/s medians of
+# five processes on MI355X (profiles/attn_sweep_mi355x.txt), the rule of the
+# floors above, with the GEMM floor's caveat: small integers clock higher than
+# random data. The device-to-device spread has not been measured; 0.70 is
+# borrowed from the MFMA floor. 0 disables a floor.
+MIN_ATTN_SWEEP_TFLOPS = {"full": 662.1, "causal": 467.5}
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -457,6 +478,31 @@ class MxQuantSweepResult:
         return (
             f"{self.sweep.describe()}; first wave {w} (workgroup {w // 4} wave {w % 4}) on "
             f"{mfma_unit_name(self.sweep.bad_simds[0])}"
+        )
+
+
+@dataclass
+class AttnSweepResult:
+    """Outcome of an attention sweep verify: the matrix-core sweep's result
+    over the 4 waves of every block of 128 queries of every head, and the rate
+    of the timed launch (0 when only a verify was done)."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    n_q: int = 0
+    tflops: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong wave by head, rows and unit."""
+        w = self.sweep.first_bad_wave
+        block, nqb = w // 4, max(self.n_q // ATTN_Q_BLOCK, 1)
+        row = block % nqb * ATTN_Q_BLOCK + w % 4 * 32
+        return (
+            f"{self.sweep.describe()}; first wave {w} (head {block // nqb} rows {row}..{row + 31})"
+            f" on {mfma_unit_name(self.sweep.bad_simds[0])}"
         )
 
 
@@ -823,6 +869,17 @@ _ABI = {
         _int, (_P(MfmaRecord), _i64, _int, _i64, _i64, _int, _int, _u64, _P(_MfmaSweepResultC))),
     "na_mxquant_sweep": (
         _int, (_int, _int, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
+    "na_attn_sweep_fill": (
+        _int, (_int, _void_p, _void_p, _void_p, _int, _int, _i64, _i64, _u64)),
+    "na_attn_sweep_expected": (_int, (_u64, _int, _int, _i64, _i64, _int, _int, _u64_p, _i64)),
+    "na_attn_run": (
+        _int, (_int, _void_p, _void_p, _void_p, _void_p, _int, _int, _i64, _i64, _int,
+               ctypes.c_float, _int, _u64, _P(MfmaRecord), _i64, _double_p)),
+    "na_attn_sweep_verify": (
+        _int, (_P(MfmaRecord), _i64, _int, _int, _i64, _i64, _int, _int, _u64,
+               _P(_MfmaSweepResultC))),
+    "na_attn_sweep": (
+        _int, (_int, _int, _int, _i64, _i64, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
 }
 
 
@@ -902,6 +959,12 @@ class GPUReport:
     mxquant_sweep_clock_mhz: float = 0.0  # fp8 run; informational, no floor
     mxquant_sweep_units_seen: int = 0
     mxquant_sweep_bad_waves: int = 0  # of the three formats
+    # chip-wide fused attention sweep (opt-in)
+    attn_sweep_tflops: float = 0.0
+    attn_sweep_causal_tflops: float = 0.0
+    attn_sweep_clock_mhz: float = 0.0  # full run; informational, no floor
+    attn_sweep_units_seen: int = 0
+    attn_sweep_bad_waves: int = 0  # of both runs
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -1945,6 +2008,90 @@ class NodeAgent:
             if not res.ok:
                 g.problems.append(f"MX quantise sweep {fmt}: {res.describe()}")
 
+    # -- chip-wide fused attention sweep ------------------------------------------
+
+    def attn_fill(self, dev: int, q: int, k: int, v: int, heads: int, kv_heads: int, n_q: int,
+                  n_k: int, seed: int = DEFAULT_ATTN_SWEEP_SEED) -> None:
+        """Write the sweep's hashed Q (``heads`` x ``n_q`` x 128 bf16) and K
+        and V (``kv_heads`` x ``n_k`` x 128) into device memory the caller
+        owns (device pointers as integers, e.g. ``tensor.data_ptr()``)."""
+        rc = self.lib.na_attn_sweep_fill(dev, q, k, v, heads, kv_heads, n_q, n_k, seed)
+        self._check(rc, f"attn_fill({dev})")
+
+    def attn_expected(self, heads: int, kv_heads: int, n_q: int, n_k: int, causal: bool = False,
+                      reps: int = 1, seed: int = DEFAULT_ATTN_SWEEP_SEED) -> list:
+        """Reference checksums of every wave of an attention sweep on
+        ``attn_fill``'s tensors, record ``4 * (head * n_q / 128 + block) +
+        wave``. Host arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * max(heads * (n_q // ATTN_Q_BLOCK) * 4, 1))()
+        rc = self.lib.na_attn_sweep_expected(seed, heads, kv_heads, n_q, n_k, int(causal), reps,
+                                             out, len(out))
+        self._check(rc, "attn_expected")
+        return list(out)
+
+    def attn_run(self, dev: int, q: int, k: int, v: int, heads: int, kv_heads: int, n_q: int,
+                 n_k: int, causal: bool = False, scale: float = ATTN_HEAD_DIM ** -0.5,
+                 reps: int = 1, seed: int = DEFAULT_ATTN_SWEEP_SEED, o: int = 0) -> tuple:
+        """One launch of fused attention, ``softmax(scale * q k^T [+ causal
+        mask]) v``, on the bf16 tensors at ``q``, ``k`` and ``v``. ``o``, when
+        not 0, is device memory for the ``heads`` x ``n_q`` x 128 float32
+        result. ``scale`` is the natural one (the kernel works in base 2, so
+        the library gets ``scale * log2(e)``); the sweep's exact checksums
+        need ``scale = ln 2``. Returns ``(records, ms)``: a ctypes array of
+        ``MfmaRecord`` and the HIP-event time."""
+        recs = (MfmaRecord * max(heads * (n_q // ATTN_Q_BLOCK) * 4, 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_attn_run(dev, q, k, v, o or None, heads, kv_heads, n_q, n_k, int(causal),
+                                  scale * math.log2(math.e), reps, seed, recs, len(recs),
+                                  ctypes.byref(ms))
+        self._check(rc, f"attn_run({dev})")
+        return recs, ms.value
+
+    def attn_verify(self, recs, heads: int, kv_heads: int, n_q: int, n_k: int,
+                    causal: bool = False, reps: int = 1,
+                    seed: int = DEFAULT_ATTN_SWEEP_SEED) -> tuple:
+        """Compare every record's checksum against the host reference of
+        ``attn_fill``'s tensors. Returns ``(rc, AttnSweepResult)``; rc is
+        ``NA_ERR_VERIFY`` on any bad wave, and ``na_last_error`` then names the
+        first by head, rows and unit."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_attn_sweep_verify(recs, len(recs), heads, kv_heads, n_q, n_k,
+                                           int(causal), reps, seed, ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, AttnSweepResult()
+        return rc, AttnSweepResult(MfmaSweepResult._from_c("bf16", res), n_q)
+
+    def attn_sweep(self, dev: int, heads: int = 0, kv_heads: int = 0, n_q: int = 0, n_k: int = 0,
+                   causal: bool = False, reps: int = 0,
+                   seed: int = DEFAULT_ATTN_SWEEP_SEED) -> AttnSweepResult:
+        """Allocate and fill Q, K and V, run the attention twice (the second
+        launch timed) and verify every wave bit-exactly. 0 selects the
+        default: 512 heads, a quarter as many KV heads, ``ATTN_SWEEP_SEQ``
+        queries and keys, 127 repetitions. Wrong waves come back in the result
+        (``.ok`` False), not as an exception."""
+        res, tflops = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_attn_sweep(dev, heads, kv_heads, n_q, n_k, int(causal), reps, seed,
+                                    ctypes.byref(res), ctypes.byref(tflops))
+        self._check(rc, f"attn_sweep({dev})", ok=(NA_OK, NA_ERR_VERIFY))
+        return AttnSweepResult(MfmaSweepResult._from_c("bf16", res, tflops.value),
+                               n_q or ATTN_SWEEP_SEQ, tflops.value)
+
+    def _run_attn_sweep(self, g: GPUReport) -> None:
+        for mode, name in (("full", "attn_sweep_tflops"), ("causal", "attn_sweep_causal_tflops")):
+            res = self.attn_sweep(g.index, causal=mode == "causal")
+            setattr(g, name, round(res.tflops, 1))
+            g.attn_sweep_bad_waves += res.sweep.bad_waves
+            if mode == "full":
+                g.attn_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+                g.attn_sweep_units_seen = res.sweep.units_seen
+            if res.tflops < MIN_ATTN_SWEEP_TFLOPS[mode]:
+                g.problems.append(
+                    f"attention sweep ({mode}) {round(res.tflops, 1)} TFLOP/s below floor "
+                    f"{MIN_ATTN_SWEEP_TFLOPS[mode]}"
+                )
+            if not res.ok:
+                g.problems.append(f"attention sweep ({mode}): {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -1963,7 +2110,8 @@ class NodeAgent:
               mx_sweep: bool = False, lds_sweep: bool = False,
               valu_sweep: bool = False, cache_sweep: bool = False,
               load_sweep: bool = False, gemm_sweep: bool = False,
-              mxgemm_sweep: bool = False, mxquant_sweep: bool = False) -> NodeReport:
+              mxgemm_sweep: bool = False, mxquant_sweep: bool = False,
+              attn_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -2040,6 +2188,13 @@ class NodeAgent:
         host's own quantiser. A wrong wave is a problem that names its format,
         workgroup and unit, as is a conversion rate under the format's
         ``MIN_MXQUANT_SWEEP_GELEMS``. False (default) makes no new library
+        call.
+
+        ``attn_sweep`` additionally runs the chip-wide fused attention sweep
+        on every GPU, once without and once with the causal mask: bf16
+        attention with GQA whose every wave is verified exactly. A wrong wave
+        is a problem that names its head, rows and unit, as is a rate under
+        ``MIN_ATTN_SWEEP_TFLOPS``. False (default) makes no new library
         call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
@@ -2094,6 +2249,8 @@ class NodeAgent:
                     self._run_mxgemm_sweep(g)
                 if mxquant_sweep:
                     self._run_mxquant_sweep(g)
+                if attn_sweep:
+                    self._run_attn_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -2277,6 +2434,15 @@ def main(argv=None) -> int:
         "in-kernel clocks (cache-resident slices: not a memory figure)",
     )
     ap.add_argument(
+        "--attn-sweep",
+        action="store_true",
+        help="also run the chip-wide fused attention sweep on every GPU: bf16 flash attention "
+        "with GQA at head dimension 128 (two chained MFMA products, online softmax, transposed "
+        "LDS reads of V), without and with the causal mask, on hashed integer operands whose "
+        "every intermediate is exact; every wave's checksum is recomputed on the host and a "
+        "wrong one attributed to its XCC/SE/SH/CU/SIMD, head and rows; reports both rates",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -2299,6 +2465,7 @@ def main(argv=None) -> int:
             gemm_sweep=args.gemm_sweep,
             mxgemm_sweep=args.mxgemm_sweep,
             mxquant_sweep=args.mxquant_sweep,
+            attn_sweep=args.attn_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

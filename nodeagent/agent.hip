@@ -29,7 +29,11 @@
 // (mxgemmsweep.h), an opt-in chip-wide MX quantise sweep (the bf16 to
 // MXFP8/FP6/FP4 quantiser that produces those operands in service, on the
 // scaled conversion instructions, also callable on caller-owned tensors,
-// mxquantsweep.h), and the xGMI peer-to-peer link matrix. The
+// mxquantsweep.h), an opt-in chip-wide fused attention sweep (bf16, causal,
+// GQA: two chained MFMA products with an online softmax between them, every
+// wave verified exactly, also callable on caller-owned tensors, attnsweep.h
+// and attnsweep.hip),
+// and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
 // sweeps" below): a further sweep starts from those.
@@ -3333,4 +3337,269 @@ extern "C" int na_mxquant_sweep(int dev, int format, int workgroups, int passes,
                                     census.clock_mhz() / 1e3;
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide fused attention sweep (specification and kernels in attnsweep.h,
+// the kernels compiled in attnsweep.hip)
+// ---------------------------------------------------------------------------
+//
+// The other hot kernel of serving: O = softmax(scale Q K^T [+ causal mask]) V
+// in bf16 with GQA, flash-attention style, one workgroup per head and block of
+// 128 queries. As a sweep on hashed integer operands every intermediate is an
+// exact f32, each wave leaves a checksum of its unnormalised O, its row sums
+// and its row maxima, and the host recomputes it with four terms per (query,
+// key) pair; as an operation (na_attn_run) it takes any bf16 tensors and a
+// scale, its seed only weighs the checksum.
+
+#include "attnsweep.h"
+
+// The whole sweep's shape. The launch is bounded by what keeps the sums exact
+// (256 * reps * n_k < 2^24) and the host verify costs heads * n_q * n_k * 4, so
+// for a given verify time the longest launch has short sequences, many heads
+// and the most repetitions the bound allows (profiles/attn_sweep_mi355x.txt).
+#define NA_ATTN_DEFAULT_HEADS 512
+#define NA_ATTN_DEFAULT_SEQ 512
+#define NA_ATTN_DEFAULT_REPS 127
+
+static bool as_shape_ok(int heads, int kv_heads, long long n_q, long long n_k, int causal,
+                        int reps) {
+    return heads >= 1 && heads <= NA_ATTN_MAX_HEADS && kv_heads >= 1 && heads % kv_heads == 0 &&
+           n_q >= AS_QBLOCK && n_q <= NA_ATTN_MAX_Q && n_q % AS_QBLOCK == 0 && n_k >= AS_TILE &&
+           n_k % AS_TILE == 0 && n_k < NA_ATTN_EXACT / 256 && (causal == 0 || causal == 1) &&
+           (causal == 0 || n_k >= n_q) && reps >= 1 && 256 * (long long)reps * n_k < NA_ATTN_EXACT &&
+           heads * (n_q / AS_QBLOCK) <= NA_MFMA_MAX_WORKGROUPS;
+}
+
+#define AS_SHAPE_WORDS                                                                          \
+    "heads in 1..%d a multiple of kv_heads >= 1 (got %d, %d), n_q a multiple of %d in %d..%d "  \
+    "(got %lld), n_k a positive multiple of %d (got %lld), causal 0 or 1 with n_k >= n_q (got " \
+    "%d), reps >= 1 and 256 * reps * n_k < 2^24 (reps %d), at most %d blocks of queries"
+#define AS_SHAPE_ARGS(heads, kv_heads, n_q, n_k, causal, reps)                               \
+    NA_ATTN_MAX_HEADS, heads, kv_heads, AS_QBLOCK, AS_QBLOCK, NA_ATTN_MAX_Q, (long long)(n_q), \
+        AS_TILE, (long long)(n_k), causal, reps, NA_MFMA_MAX_WORKGROUPS
+
+static long long as_records(int heads, long long n_q) {
+    return heads * (n_q / AS_QBLOCK) * MS_WAVES_PER_WG;
+}
+
+// Every wave's checksum by the formula at the top of attnsweep.h: per KV head
+// u, e and Vz[j] = sum_c z_c V[j][c]; per row its 128 signs and q . u; per
+// visible pair the four signs at e_j's columns.
+static void as_expected(uint64_t base, int heads, int kv_heads, long long n_q, long long n_k,
+                        int causal, int reps, uint64_t* out) {
+    const as_layout at = as_layout_of(base, (uint64_t)heads, (uint64_t)kv_heads, (uint64_t)n_q,
+                                      (uint64_t)n_k);
+    const int group = heads / kv_heads;
+    const long long off = n_k - n_q;
+    uint64_t z[AS_D];
+    for (int c = 0; c < AS_D; ++c) z[c] = as_weight(at.w + (uint64_t)c);
+    const uint64_t wa = as_weight(at.w + AS_D), wb = as_weight(at.w + AS_D + 1);
+    std::fill(out, out + as_records(heads, n_q), (uint64_t)0);
+    std::vector<uint64_t> vz((size_t)n_k);
+    std::vector<unsigned char> column((size_t)n_k * 4);
+    std::vector<signed char> value((size_t)n_k * 4), t((size_t)n_k);
+    for (int hk = 0; hk < kv_heads; ++hk) {
+        int u[AS_D];
+        for (int c = 0; c < AS_D; ++c) u[c] = as_ternary(at.u + (uint64_t)(hk * AS_D + c));
+        for (long long j = 0; j < n_k; ++j) {
+            const uint64_t row = (uint64_t)(hk * n_k + j);
+            uint64_t sum = 0;
+            for (int c = 0; c < AS_D; ++c)
+                sum += z[c] * (uint64_t)(int64_t)as_ternary(at.v + row * AS_D + (uint64_t)c);
+            vz[(size_t)j] = sum;
+            for (int quarter = 0; quarter < 4; ++quarter) {
+                int col, val;
+                as_e(at.e + row * 4 + (uint64_t)quarter, &col, &val);
+                column[(size_t)(4 * j + quarter)] = (unsigned char)(32 * quarter + col);
+                value[(size_t)(4 * j + quarter)] = (signed char)val;
+            }
+        }
+        for (int h = hk * group; h < (hk + 1) * group; ++h)
+            for (long long i = 0; i < n_q; ++i) {
+                signed char sign[AS_D];
+                int common = 0;
+                for (int c = 0; c < AS_D; ++c) {
+                    const unsigned bits = as_q_bits(at.q + (uint64_t)((h * n_q + i) * 8 + c / 16));
+                    sign[c] = (bits >> (c % 16) & 1) ? 1 : -1;
+                    common += sign[c] * u[c];
+                }
+                const long long visible = causal ? std::min(n_k, i + off + 1) : n_k;
+                int top = -4;
+                for (long long j = 0; j < visible; ++j) {
+                    const unsigned char* const col = &column[(size_t)(4 * j)];
+                    const signed char* const val = &value[(size_t)(4 * j)];
+                    const int s = val[0] * sign[col[0]] + val[1] * sign[col[1]] +
+                                  val[2] * sign[col[2]] + val[3] * sign[col[3]];
+                    t[(size_t)j] = (signed char)s;
+                    top = std::max(top, s);
+                }
+                uint64_t l256 = 0, o256 = 0;  // 256 l and sum_c z_c 256 O[i][c] of one walk
+                for (long long j = 0; j < visible; ++j) {
+                    const uint64_t p256 = (uint64_t)1 << (8 + t[(size_t)j] - top);
+                    l256 += p256;
+                    o256 += p256 * vz[(size_t)j];
+                }
+                const uint64_t row = (uint64_t)reps * (o256 + wa * l256) +
+                                     wb * (uint64_t)(int64_t)(common + top);
+                out[(h * (n_q / AS_QBLOCK) + i / AS_QBLOCK) * MS_WAVES_PER_WG +
+                    i % AS_QBLOCK / AS_WAVE_ROWS] +=
+                    as_weight(at.w + AS_WEIGHTS + (uint64_t)(h * n_q + i)) * row;
+            }
+    }
+}
+
+// Pure host code: all 4 * heads * n_q / 128 checksums, n_out exactly that.
+extern "C" int na_attn_sweep_expected(unsigned long long seed, int heads, int kv_heads,
+                                      long long n_q, long long n_k, int causal, int reps,
+                                      uint64_t* checksums, long long n_out) {
+    if (!as_shape_ok(heads, kv_heads, n_q, n_k, causal, reps) || checksums == nullptr ||
+        n_out != as_records(heads, n_q))
+        return arg_error("na_attn_sweep_expected: need " AS_SHAPE_WORDS
+                         " and room for exactly 4 checksums per block (checksums %p, n_out %lld)",
+                         AS_SHAPE_ARGS(heads, kv_heads, n_q, n_k, causal, reps), (void*)checksums,
+                         n_out);
+    as_expected(seed * MS_G, heads, kv_heads, n_q, n_k, causal, reps, checksums);
+    return NA_OK;
+}
+
+// What the entry points that touch operands check, ahead of any HIP call.
+static int as_operand_args(const char* fn, const void* q, const void* k, const void* v, int heads,
+                           int kv_heads, long long n_q, long long n_k, int causal, int reps) {
+    if (!as_shape_ok(heads, kv_heads, n_q, n_k, causal, reps))
+        return arg_error("%s: need " AS_SHAPE_WORDS, fn,
+                         AS_SHAPE_ARGS(heads, kv_heads, n_q, n_k, causal, reps));
+    if (q == nullptr || k == nullptr || v == nullptr ||
+        (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) != 0)
+        return arg_error("%s: need 16-byte aligned q, k and v (got %p, %p, %p)", fn, q, k, v);
+    return NA_OK;
+}
+
+// Writes the sweep's Q, K and V of `seed` into caller-owned device memory.
+extern "C" int na_attn_sweep_fill(int dev, void* q, void* k, void* v, int heads, int kv_heads,
+                                  long long n_q, long long n_k, unsigned long long seed) {
+    int rc = as_operand_args("na_attn_sweep_fill", q, k, v, heads, kv_heads, n_q, n_k, 0, 1);
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t q_vecs = (uint64_t)heads * (uint64_t)n_q * AS_ROW_VECS;
+    const uint64_t kv_vecs = (uint64_t)kv_heads * (uint64_t)n_k * AS_ROW_VECS;
+    const unsigned grid = (unsigned)((q_vecs + 2 * kv_vecs + MS_BLOCK - 1) / MS_BLOCK);
+    as_launch_fill(grid, static_cast<mt_vec*>(q), static_cast<mt_vec*>(k), static_cast<mt_vec*>(v),
+                   q_vecs, kv_vecs, (uint64_t)n_k,
+                   as_layout_of(seed * MS_G, (uint64_t)heads, (uint64_t)kv_heads, (uint64_t)n_q,
+                                (uint64_t)n_k));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// One launch of one workgroup per head and block of 128 queries on caller-owned
+// tensors, HIP-event timed: any bf16 q, k and v inside the contract; o, when
+// not null, receives the normalised output (the sweep passes null); records
+// receives the 4 records per block, whose checksums match
+// na_attn_sweep_expected when the tensors are na_attn_sweep_fill's of the same
+// seed and shape and scale_log2 is 1. Argument errors are detected before any
+// HIP call.
+extern "C" int na_attn_run(int dev, const void* q, const void* k, const void* v, void* o,
+                           int heads, int kv_heads, long long n_q, long long n_k, int causal,
+                           float scale_log2, int reps, unsigned long long seed,
+                           na_mfma_record* records, long long n_out, double* ms) {
+    int rc = as_operand_args("na_attn_run", q, k, v, heads, kv_heads, n_q, n_k, causal, reps);
+    if (rc != NA_OK) return rc;
+    if (!(scale_log2 > 0.f) || !std::isfinite(scale_log2) || ((uintptr_t)o & 15) != 0)
+        return arg_error("na_attn_run: need a finite scale_log2 > 0 (got %g) and o null or "
+                         "16-byte aligned (%p)",
+                         (double)scale_log2, o);
+    if (records == nullptr || n_out != as_records(heads, n_q))
+        return arg_error("na_attn_run: need room for exactly 4 records per block (records %p, "
+                         "n_out %lld, want %lld)",
+                         (void*)records, n_out, as_records(heads, n_q));
+    size_t lds_bytes = 0;
+    rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes < AS_LDS_BYTES)
+        return arg_error("na_attn_run: the device's %zu-byte per-workgroup LDS allocation is "
+                         "under the %d bytes of the two stages",
+                         lds_bytes, AS_LDS_BYTES);
+    const uint32_t nqb = (uint32_t)(n_q / AS_QBLOCK), nkt = (uint32_t)(n_k / AS_TILE);
+    const as_layout at = as_layout_of(seed * MS_G, (uint64_t)heads, (uint64_t)kv_heads,
+                                      (uint64_t)n_q, (uint64_t)n_k);
+    return sweep_launch(dev, (size_t)n_out, records, ms, [&](na_mfma_record* recs) {
+        as_launch_sweep(recs, static_cast<const mt_vec*>(q), static_cast<const mt_vec*>(k),
+                        static_cast<const mt_vec*>(v), static_cast<float*>(o), (uint32_t)heads,
+                        (uint32_t)(heads / kv_heads), nqb, nkt, (uint32_t)causal, scale_log2,
+                        (uint32_t)reps, at.w);
+    });
+}
+
+// Pure host code: record i is wave i % 4 of block i / 4 = head * n_q / 128 +
+// query block. Returns NA_ERR_VERIFY on any bad wave (ms_tally's rules), with
+// a message that names the first; *res is filled either way.
+extern "C" int na_attn_sweep_verify(const na_mfma_record* recs, long long n, int heads,
+                                    int kv_heads, long long n_q, long long n_k, int causal,
+                                    int reps, unsigned long long seed, na_mfma_sweep_result* res) {
+    if (!as_shape_ok(heads, kv_heads, n_q, n_k, causal, reps) || recs == nullptr ||
+        n != as_records(heads, n_q) || res == nullptr)
+        return arg_error("na_attn_sweep_verify: need " AS_SHAPE_WORDS
+                         ", exactly 4 records per block (recs %p, n %lld) and a result pointer",
+                         AS_SHAPE_ARGS(heads, kv_heads, n_q, n_k, causal, reps),
+                         (const void*)recs, n);
+    std::vector<uint64_t> want((size_t)n);
+    as_expected(seed * MS_G, heads, kv_heads, n_q, n_k, causal, reps, want.data());
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const unsigned long long w = res->first_bad_wave, block = w / MS_WAVES_PER_WG;
+    const unsigned long long nqb = (unsigned long long)(n_q / AS_QBLOCK);
+    return na_error(NA_ERR_VERIFY,
+                    "attn sweep: %llu of %llu waves wrong on %llu CU(s), first wave %llu (head "
+                    "%llu rows %llu..%llu) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, block / nqb,
+                    block % nqb * AS_QBLOCK + w % MS_WAVES_PER_WG * AS_WAVE_ROWS,
+                    block % nqb * AS_QBLOCK + w % MS_WAVES_PER_WG * AS_WAVE_ROWS + AS_WAVE_ROWS - 1,
+                    u[0], u[1], u[2], u[3], u[4]);
+}
+
+// Whole sweep on tensors the agent allocates and fills itself: one untimed
+// warm-up launch, the timed launch, the verify. 0 = default for heads (512),
+// kv_heads (heads / 4, or heads when 4 does not divide them), n_q and n_k (512)
+// and reps (127). *tflops counts 4 * 128 * reps FLOP per visible (query, key)
+// pair over the event time.
+extern "C" int na_attn_sweep(int dev, int heads, int kv_heads, long long n_q, long long n_k,
+                             int causal, int reps, unsigned long long seed,
+                             na_mfma_sweep_result* res, double* tflops) {
+    if (res == nullptr || heads < 0 || kv_heads < 0 || n_q < 0 || n_k < 0 || reps < 0)
+        return arg_error("na_attn_sweep: need heads, kv_heads, n_q, n_k and reps >= 0 (got %d, %d, "
+                         "%lld, %lld, %d) and a result pointer",
+                         heads, kv_heads, n_q, n_k, reps);
+    if (heads == 0) heads = NA_ATTN_DEFAULT_HEADS;
+    if (kv_heads == 0) kv_heads = heads % 4 == 0 ? heads / 4 : heads;
+    if (n_q == 0) n_q = NA_ATTN_DEFAULT_SEQ;
+    if (n_k == 0) n_k = NA_ATTN_DEFAULT_SEQ;
+    if (reps == 0) reps = NA_ATTN_DEFAULT_REPS;
+    if (!as_shape_ok(heads, kv_heads, n_q, n_k, causal, reps))
+        return arg_error("na_attn_sweep: need " AS_SHAPE_WORDS,
+                         AS_SHAPE_ARGS(heads, kv_heads, n_q, n_k, causal, reps));
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<unsigned char> q, k, v;
+    HIP_CHECK(q.alloc((size_t)heads * (size_t)n_q * AS_D * 2));
+    HIP_CHECK(k.alloc((size_t)kv_heads * (size_t)n_k * AS_D * 2));
+    HIP_CHECK(v.alloc((size_t)kv_heads * (size_t)n_k * AS_D * 2));
+    int rc = na_attn_sweep_fill(dev, q.p, k.p, v.p, heads, kv_heads, n_q, n_k, seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs((size_t)as_records(heads, n_q));
+    double ms = 0.0;
+    rc = sweep_twice([&] {
+        return na_attn_run(dev, q.p, k.p, v.p, nullptr, heads, kv_heads, n_q, n_k, causal, 1.0f,
+                           reps, seed, recs.data(), (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
+    if (tflops) {
+        double pairs = (double)n_q * (double)n_k;
+        if (causal) pairs -= (double)n_q * (double)(n_q - 1) / 2.0;  // rows see n_k - n_q + i + 1
+        *tflops = 4.0 * AS_D * pairs * heads * reps / (ms * 1e9);
+    }
+    return na_attn_sweep_verify(recs.data(), (long long)recs.size(), heads, kv_heads, n_q, n_k,
+                                causal, reps, seed, res);
 }

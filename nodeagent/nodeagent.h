@@ -51,6 +51,12 @@
 #define NA_MXQUANT_BLOCK 32      // the MX quantiser's K is a multiple of this: elements per scale,
 #define NA_MXQUANT_MAX_BLOCKS (1 << 24)  // rows * K / 32 is at most this (1 GiB of bf16),
 #define NA_MXQUANT_MAX_PASSES (1 << 20)  // and a launch repeats its slice at most this often
+#define NA_ATTN_HEAD_DIM 128     // the attention sweep's head dimension;
+#define NA_ATTN_Q_BLOCK 128      // its n_q is a multiple of this,
+#define NA_ATTN_K_TILE 64        // its n_k of this,
+#define NA_ATTN_MAX_HEADS 4096   // with at most this many heads
+#define NA_ATTN_MAX_Q (1 << 20)  // of at most this many queries,
+#define NA_ATTN_EXACT (1 << 24)  // and 256 * reps * n_k stays under this: exact f32 sums
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -66,6 +72,9 @@
 // clocks around the K loops, and the MX GEMM sweep (mxgemmsweep.h) the same.
 // The MX quantise sweep (mxquantsweep.h) leaves it for each wave of each
 // workgroup, `wave` being 4 * workgroup + wave and the clocks around the passes.
+// The attention sweep (attnsweep.h) leaves it for each wave of each block of
+// 128 queries of each head, `wave` being 4 * (head * n_q / 128 + block) + wave
+// and the clocks around the walk over the keys.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -349,6 +358,29 @@ int na_mxquant_verify(const na_mfma_record* recs, long long n, int format, long 
                       na_mfma_sweep_result* res);
 int na_mxquant_sweep(int dev, int format, int workgroups, int passes, unsigned long long seed,
                      na_mfma_sweep_result* res, double* gelems);
+
+// chip-wide fused attention sweep, and the attention it runs as an operation on
+// caller-owned tensors: o = softmax(scale q k^T [+ causal mask]) v in base 2,
+// p = exp2(scale_log2 * (s - max s)); q is bf16[heads][n_q][128], k and v
+// bf16[kv_heads][n_k][128], row-major, o null or float[heads][n_q][128]; n_q a
+// multiple of 128, n_k of 64, heads of kv_heads (query head h reads KV head h /
+// (heads / kv_heads)); causal 1 shows key j to query i iff j <= i + n_k - n_q and
+// needs n_k >= n_q; reps walks the keys that often into one softmax state;
+// operands, layout and checksum in attnsweep.h; records and results are the
+// matrix-core sweep's, record 4 * (head * n_q / 128 + block) + wave
+int na_attn_sweep_fill(int dev, void* q, void* k, void* v, int heads, int kv_heads, long long n_q,
+                       long long n_k, unsigned long long seed);
+int na_attn_sweep_expected(unsigned long long seed, int heads, int kv_heads, long long n_q,
+                           long long n_k, int causal, int reps, uint64_t* checksums,
+                           long long n_out);
+int na_attn_run(int dev, const void* q, const void* k, const void* v, void* o, int heads,
+                int kv_heads, long long n_q, long long n_k, int causal, float scale_log2, int reps,
+                unsigned long long seed, na_mfma_record* records, long long n_out, double* ms);
+int na_attn_sweep_verify(const na_mfma_record* recs, long long n, int heads, int kv_heads,
+                         long long n_q, long long n_k, int causal, int reps,
+                         unsigned long long seed, na_mfma_sweep_result* res);
+int na_attn_sweep(int dev, int heads, int kv_heads, long long n_q, long long n_k, int causal,
+                  int reps, unsigned long long seed, na_mfma_sweep_result* res, double* tflops);
 
 #ifdef __cplusplus
 }
