@@ -8,7 +8,7 @@ there is no eager/python fallback for the hardware checks.
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
 [--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]
-[--mxquant-sweep] [--attn-sweep]``
+[--mxquant-sweep] [--attn-sweep] [--decode-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -245,6 +245,26 @@ ATTN_SWEEP_SEQ = 512  # agent.hip: NA_ATTN_DEFAULT_SEQ, the default n_q and n_k
 # random data. The device-to-device spread has not been measured; 0.70 is
 # borrowed from the MFMA floor. 0 disables a floor.
 MIN_ATTN_SWEEP_TFLOPS = {"full": 662.1, "causal": 467.5}
+
+# Chip-wide paged decode attention sweep (nodeagent/decodesweep.h): one query
+# token per sequence against a KV cache in pages of 16 tokens reached through a
+# block table, bf16 with GQA at head dimension 128, the walk over the keys
+# split across the waves of ``splits`` workgroups per (sequence, KV head) and
+# merged in LDS and by a combine kernel; bound by HBM, so the figure is bytes
+# of KV per second. Also an operation on caller-owned tensors (``decode_run``).
+# The default seed is "MI355XDC"; ``batch * kv_heads * (4 * splits + 1)``
+# records, results are the matrix-core sweep's.
+DEFAULT_DECODE_SWEEP_SEED = 0x4D493335_35584443
+# nodeagent/nodeagent.h: NA_DECODE_PAGE, NA_DECODE_MAX_GROUP, NA_DECODE_MAX_SPLITS
+DECODE_PAGE = 16  # tokens per page of the KV cache
+DECODE_MAX_GROUP = 16  # heads / kv_heads is at most this
+DECODE_MAX_SPLITS = 64
+# Floor of the default sweep (64 sequences of 32 heads on 4 KV heads, up to
+# 8192 tokens, 7 repetitions) in GB of KV per second: 0.70 x the 5529.6 GB/s
+# median of five processes on MI355X (profiles/decode_sweep_mi355x.txt), the
+# rule of the floors above. The device-to-device spread has not been measured;
+# 0.70 is borrowed from the MFMA floor. 0 disables the floor.
+MIN_DECODE_SWEEP_GBPS = 3870.7
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -503,6 +523,40 @@ class AttnSweepResult:
         return (
             f"{self.sweep.describe()}; first wave {w} (head {block // nqb} rows {row}..{row + 31})"
             f" on {mfma_unit_name(self.sweep.bad_simds[0])}"
+        )
+
+
+@dataclass
+class DecodeSweepResult:
+    """Outcome of a decode attention sweep verify: the matrix-core sweep's
+    result over the 4 wave records of every split of every (sequence, KV head)
+    and the final record of each, and the KV bytes per second of the timed
+    launch in GB/s (0 when only a verify was done)."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    batch: int = 0
+    kv_heads: int = 0
+    splits: int = 0
+    gbps: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong record by sequence, KV
+        head, split and wave (or as a final state) and unit."""
+        w, kv = self.sweep.first_bad_wave, max(self.kv_heads, 1)
+        finals = self.batch * kv * self.splits * 4
+        if w < finals:
+            item = w // 4 // max(self.splits, 1)
+            what = (f"sequence {item // kv} KV head {item % kv} split {w // 4 % self.splits} "
+                    f"wave {w % 4}")
+        else:
+            what = f"final state of sequence {(w - finals) // kv} KV head {(w - finals) % kv}"
+        return (
+            f"{self.sweep.describe()}; first record {w} ({what}) on "
+            f"{mfma_unit_name(self.sweep.bad_simds[0])}"
         )
 
 
@@ -880,6 +934,20 @@ _ABI = {
                _P(_MfmaSweepResultC))),
     "na_attn_sweep": (
         _int, (_int, _int, _int, _i64, _i64, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
+    "na_decode_splits": (_int, (_int, _int, _int, _int, _int_p)),
+    "na_decode_sweep_fill": (
+        _int, (_int, _void_p, _void_p, _void_p, _void_p, _void_p, _int, _int, _int, _int, _int_p,
+               _u64)),
+    "na_decode_sweep_expected": (
+        _int, (_u64, _int, _int, _int, _int, _int_p, _int, _int, _u64_p, _i64)),
+    "na_decode_run": (
+        _int, (_int, _void_p, _void_p, _void_p, _void_p, _void_p, _void_p, _int, _int, _int, _int,
+               _i64, _int, ctypes.c_float, _int, _u64, _P(MfmaRecord), _i64, _double_p)),
+    "na_decode_sweep_verify": (
+        _int, (_P(MfmaRecord), _i64, _int, _int, _int, _int, _int_p, _int, _int, _u64,
+               _P(_MfmaSweepResultC))),
+    "na_decode_sweep": (
+        _int, (_int, _int, _int, _int, _int, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
 }
 
 
@@ -965,6 +1033,11 @@ class GPUReport:
     attn_sweep_clock_mhz: float = 0.0  # full run; informational, no floor
     attn_sweep_units_seen: int = 0
     attn_sweep_bad_waves: int = 0  # of both runs
+    # chip-wide paged decode attention sweep (opt-in)
+    decode_sweep_gbps: float = 0.0  # GB of KV per second
+    decode_sweep_clock_mhz: float = 0.0  # informational, no floor
+    decode_sweep_units_seen: int = 0
+    decode_sweep_bad_waves: int = 0  # wave records and final records
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -2092,6 +2165,112 @@ class NodeAgent:
             if not res.ok:
                 g.problems.append(f"attention sweep ({mode}): {res.describe()}")
 
+    # -- chip-wide paged decode attention sweep -----------------------------------
+
+    def decode_splits(self, dev: int, batch: int, kv_heads: int, max_pages: int) -> int:
+        """The ``splits`` that ``decode_sweep`` takes for 0: about two
+        workgroups per CU of device ``dev``."""
+        out = ctypes.c_int(0)
+        rc = self.lib.na_decode_splits(dev, batch, kv_heads, max_pages, ctypes.byref(out))
+        self._check(rc, f"decode_splits({dev})")
+        return out.value
+
+    def decode_fill(self, dev: int, q: int, k_cache: int, v_cache: int, block_table: int,
+                    seq_lens: int, batch: int, heads: int, kv_heads: int, max_pages: int,
+                    lens, seed: int = DEFAULT_DECODE_SWEEP_SEED) -> None:
+        """Write the sweep's hashed q (``batch`` x ``heads`` x 128 bf16), the
+        paged K and V (``batch * max_pages + 1`` pages of ``kv_heads`` x 16 x
+        128, the last one and every slot beyond a length NaN), the int32 block
+        table and the device copy of the lengths ``lens`` into device memory
+        the caller owns (device pointers as integers)."""
+        rc = self.lib.na_decode_sweep_fill(dev, q, k_cache, v_cache, block_table, seq_lens, batch,
+                                           heads, kv_heads, max_pages,
+                                           (ctypes.c_int * len(lens))(*lens), seed)
+        self._check(rc, f"decode_fill({dev})")
+
+    def decode_expected(self, batch: int, heads: int, kv_heads: int, max_pages: int, lens,
+                        splits: int = 1, reps: int = 1,
+                        seed: int = DEFAULT_DECODE_SWEEP_SEED) -> list:
+        """Reference checksums of every record of a decode sweep on
+        ``decode_fill``'s tensors: ``4 * ((b * kv_heads + hk) * splits + split)
+        + wave``, then one per (sequence, KV head) over the merged state. Host
+        arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * max(batch * kv_heads * (4 * splits + 1), 1))()
+        rc = self.lib.na_decode_sweep_expected(seed, batch, heads, kv_heads, max_pages,
+                                               (ctypes.c_int * len(lens))(*lens), splits, reps,
+                                               out, len(out))
+        self._check(rc, "decode_expected")
+        return list(out)
+
+    def decode_run(self, dev: int, q: int, k_cache: int, v_cache: int, block_table: int,
+                   seq_lens: int, batch: int, heads: int, kv_heads: int, max_pages: int,
+                   num_pages: int, splits: int = 1, scale: float = ATTN_HEAD_DIM ** -0.5,
+                   reps: int = 1, seed: int = DEFAULT_DECODE_SWEEP_SEED, o: int = 0) -> tuple:
+        """One launch of paged decode attention: one bf16 query token per
+        sequence at ``q`` against the pages of ``k_cache`` and ``v_cache`` that
+        ``block_table`` (int32 ``batch`` x ``max_pages``) names for the first
+        ``seq_lens`` (int32) tokens, all device memory. ``o``, when not 0, is
+        device memory for the ``batch`` x ``heads`` x 128 float32 result.
+        ``scale`` is the natural one; the sweep's exact checksums need ``scale
+        = ln 2``. Returns ``(records, ms)``."""
+        recs = (MfmaRecord * max(batch * kv_heads * (4 * splits + 1), 1))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_decode_run(dev, q, k_cache, v_cache, block_table, seq_lens, o or None,
+                                    batch, heads, kv_heads, max_pages, num_pages, splits,
+                                    scale * math.log2(math.e), reps, seed, recs, len(recs),
+                                    ctypes.byref(ms))
+        self._check(rc, f"decode_run({dev})")
+        return recs, ms.value
+
+    def decode_verify(self, recs, batch: int, heads: int, kv_heads: int, max_pages: int, lens,
+                      splits: int = 1, reps: int = 1,
+                      seed: int = DEFAULT_DECODE_SWEEP_SEED) -> tuple:
+        """Compare every record's checksum against the host reference of
+        ``decode_fill``'s tensors. Returns ``(rc, DecodeSweepResult)``; rc is
+        ``NA_ERR_VERIFY`` on any bad record, and ``na_last_error`` then names
+        the first by sequence, KV head, split and wave."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_decode_sweep_verify(recs, len(recs), batch, heads, kv_heads, max_pages,
+                                             (ctypes.c_int * len(lens))(*lens), splits, reps,
+                                             seed, ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, DecodeSweepResult()
+        return rc, DecodeSweepResult(MfmaSweepResult._from_c("bf16", res), batch, kv_heads, splits)
+
+    def decode_sweep(self, dev: int, batch: int = 0, heads: int = 0, kv_heads: int = 0,
+                     max_pages: int = 0, splits: int = 0, reps: int = 0,
+                     seed: int = DEFAULT_DECODE_SWEEP_SEED) -> DecodeSweepResult:
+        """Allocate and fill the paged tensors with hashed mixed lengths, run
+        the decode attention twice (the second launch timed) and verify every
+        record bit-exactly. 0 selects the default: 64 sequences, 32 heads, an
+        eighth as many KV heads, 512 pages (8192 tokens) a sequence, about two
+        workgroups per CU, the most repetitions the exactness bound allows.
+        Wrong records come back in the result (``.ok`` False), not as an
+        exception."""
+        res, gbps = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_decode_sweep(dev, batch, heads, kv_heads, max_pages, splits, reps, seed,
+                                      ctypes.byref(res), ctypes.byref(gbps))
+        self._check(rc, f"decode_sweep({dev})", ok=(NA_OK, NA_ERR_VERIFY))
+        batch, heads = batch or 64, heads or 32
+        kv_heads = kv_heads or (heads // 8 if heads % 8 == 0 else heads)
+        splits = splits or self.decode_splits(dev, batch, kv_heads, max_pages or 512)
+        return DecodeSweepResult(MfmaSweepResult._from_c("bf16", res), batch, kv_heads, splits,
+                                 gbps.value)
+
+    def _run_decode_sweep(self, g: GPUReport) -> None:
+        res = self.decode_sweep(g.index)
+        g.decode_sweep_gbps = round(res.gbps, 1)
+        g.decode_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+        g.decode_sweep_units_seen = res.sweep.units_seen
+        g.decode_sweep_bad_waves = res.sweep.bad_waves
+        if res.gbps < MIN_DECODE_SWEEP_GBPS:
+            g.problems.append(
+                f"decode attention sweep {round(res.gbps, 1)} GB/s of KV below floor "
+                f"{MIN_DECODE_SWEEP_GBPS}"
+            )
+        if not res.ok:
+            g.problems.append(f"decode attention sweep: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -2111,7 +2290,7 @@ class NodeAgent:
               valu_sweep: bool = False, cache_sweep: bool = False,
               load_sweep: bool = False, gemm_sweep: bool = False,
               mxgemm_sweep: bool = False, mxquant_sweep: bool = False,
-              attn_sweep: bool = False) -> NodeReport:
+              attn_sweep: bool = False, decode_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -2195,7 +2374,15 @@ class NodeAgent:
         attention with GQA whose every wave is verified exactly. A wrong wave
         is a problem that names its head, rows and unit, as is a rate under
         ``MIN_ATTN_SWEEP_TFLOPS``. False (default) makes no new library
-        call."""
+        call.
+
+        ``decode_sweep`` additionally runs the chip-wide paged decode
+        attention sweep on every GPU: one query token per sequence against a
+        paged bf16 KV cache of mixed lengths, every wave's softmax state and
+        every merged state verified exactly. A wrong record is a problem that
+        names its sequence, KV head, split, wave and unit, as is a rate of KV
+        bytes under ``MIN_DECODE_SWEEP_GBPS``. False (default) makes no new
+        library call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -2251,6 +2438,8 @@ class NodeAgent:
                     self._run_mxquant_sweep(g)
                 if attn_sweep:
                     self._run_attn_sweep(g)
+                if decode_sweep:
+                    self._run_decode_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -2443,6 +2632,17 @@ def main(argv=None) -> int:
         "wrong one attributed to its XCC/SE/SH/CU/SIMD, head and rows; reports both rates",
     )
     ap.add_argument(
+        "--decode-sweep",
+        action="store_true",
+        help="also run the chip-wide paged decode attention sweep on every GPU: one bf16 query "
+        "token per sequence against a KV cache in pages of 16 tokens reached through a block "
+        "table, the heads of a GQA group in the MFMA's query columns, mixed lengths, the walk "
+        "split over waves and workgroups and merged in LDS and by a combine kernel; every "
+        "wave's and every merged softmax state is recomputed on the host and a wrong one "
+        "attributed to its XCC/SE/SH/CU/SIMD, sequence, KV head, split and wave; reports the "
+        "KV bytes per second",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -2466,6 +2666,7 @@ def main(argv=None) -> int:
             mxgemm_sweep=args.mxgemm_sweep,
             mxquant_sweep=args.mxquant_sweep,
             attn_sweep=args.attn_sweep,
+            decode_sweep=args.decode_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

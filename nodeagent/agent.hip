@@ -32,7 +32,11 @@
 // mxquantsweep.h), an opt-in chip-wide fused attention sweep (bf16, causal,
 // GQA: two chained MFMA products with an online softmax between them, every
 // wave verified exactly, also callable on caller-owned tensors, attnsweep.h
-// and attnsweep.hip),
+// and attnsweep.hip), an opt-in chip-wide paged decode attention sweep (one
+// query token per sequence against a bf16 KV cache in pages behind a block
+// table, split-KV with a merge of softmax states, every wave and every merged
+// state verified exactly, also callable on caller-owned tensors,
+// decodesweep.h),
 // and the xGMI peer-to-peer link matrix. The
 // chip-wide sweeps share their device-side stamp and placement record
 // (sweep_common.h) and their host side ("Shared host side of the chip-wide
@@ -3602,4 +3606,384 @@ extern "C" int na_attn_sweep(int dev, int heads, int kv_heads, long long n_q, lo
     }
     return na_attn_sweep_verify(recs.data(), (long long)recs.size(), heads, kv_heads, n_q, n_k,
                                 causal, reps, seed, res);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide paged decode attention sweep (specification and kernels in
+// decodesweep.h, the kernels compiled in attnsweep.hip)
+// ---------------------------------------------------------------------------
+//
+// Attention in decode: one query token per sequence against a KV cache in
+// pages of 16 tokens reached through a block table, the heads of a GQA group
+// in the MFMA's query columns, the walk split over the four waves of `splits`
+// workgroups per (sequence, KV head) and merged in LDS and by a combine
+// kernel. Bound by HBM: the figure is bytes of KV per second. As a sweep every
+// wave's state before any merge, and every merged state, is recomputed by the
+// host bit for bit; as an operation (na_decode_run) it takes any bf16 tensors.
+
+#include "decodesweep.h"
+
+// The whole sweep's shape: 64 sequences of 32 heads on 4 KV heads, up to 8192
+// tokens each, lengths hashed between a quarter of that and all of it (640 MiB
+// of KV a pass on average, more than the 256 MiB Infinity Cache), two splits on
+// a chip of 256 CUs, and the most repetitions the bound allows
+// (profiles/decode_sweep_mi355x.txt).
+#define NA_DECODE_DEFAULT_BATCH 64
+#define NA_DECODE_DEFAULT_HEADS 32
+#define NA_DECODE_DEFAULT_KV_HEADS 4
+#define NA_DECODE_DEFAULT_PAGES 512
+
+static bool ds_shape_ok(int batch, int heads, int kv_heads, int max_pages, int splits, int reps) {
+    return batch >= 1 && batch <= NA_DECODE_MAX_BATCH && heads >= 1 &&
+           heads <= NA_DECODE_MAX_HEADS && kv_heads >= 1 && heads % kv_heads == 0 &&
+           heads / kv_heads <= NA_DECODE_MAX_GROUP && max_pages >= 1 &&
+           max_pages <= NA_DECODE_MAX_PAGES && splits >= 1 && splits <= NA_DECODE_MAX_SPLITS &&
+           reps >= 1 && reps < NA_DECODE_EXACT / 256 &&
+           (long long)batch * kv_heads * splits <= NA_MFMA_MAX_WORKGROUPS;
+}
+
+#define DS_SHAPE_WORDS                                                                           \
+    "batch in 1..%d (got %d), heads in 1..%d a multiple of kv_heads >= 1 with heads / kv_heads " \
+    "<= %d (got %d, %d), max_pages in 1..%d (got %d), splits in 1..%d (got %d), reps in 1..%d "  \
+    "(got %d), at most %d workgroups"
+#define DS_SHAPE_ARGS(batch, heads, kv_heads, max_pages, splits, reps)                        \
+    NA_DECODE_MAX_BATCH, batch, NA_DECODE_MAX_HEADS, NA_DECODE_MAX_GROUP, heads, kv_heads,    \
+        NA_DECODE_MAX_PAGES, max_pages, NA_DECODE_MAX_SPLITS, splits, NA_DECODE_EXACT / 256 - 1, \
+        reps, NA_MFMA_MAX_WORKGROUPS
+
+// The first sequence whose length is outside 1 .. 16 max_pages or breaks the
+// exactness bound with `reps`; -1 for none.
+static int ds_bad_length(const int* lens, int batch, int max_pages, int reps) {
+    for (int b = 0; b < batch; ++b)
+        if (lens[b] < 1 || lens[b] > DS_PAGE * max_pages ||
+            256 * (long long)reps * lens[b] >= NA_DECODE_EXACT)
+            return b;
+    return -1;
+}
+
+#define DS_LENGTH_WORDS "every length in 1..16 * max_pages with 256 * reps * length < 2^24"
+
+static long long ds_records(int batch, int kv_heads, int splits) {
+    return (long long)batch * kv_heads * (MS_WAVES_PER_WG * splits + 1);
+}
+
+// Every record's checksum by the formula at the top of decodesweep.h: per
+// (sequence, KV head) u, e and Vz[j] of its len keys; per head of the group its
+// signs, q . u and the four-term logit of every key; then per wave of every
+// split, and once over all keys, maximum, 256 l and sum_c z_c 256 O.
+static void ds_expected(uint64_t base, int batch, int heads, int kv_heads, int max_pages,
+                        const int* lens, int splits, int reps, uint64_t* out) {
+    const uint64_t n_k = (uint64_t)max_pages * DS_PAGE;
+    const as_layout at = as_layout_of(base, (uint64_t)batch * heads, (uint64_t)batch * kv_heads, 1,
+                                      n_k);
+    const int group = heads / kv_heads;
+    const long long finals = (long long)batch * kv_heads * splits * MS_WAVES_PER_WG;
+    uint64_t z[AS_D];
+    for (int c = 0; c < AS_D; ++c) z[c] = as_weight(at.w + (uint64_t)c);
+    const uint64_t wa = as_weight(at.w + AS_D), wb = as_weight(at.w + AS_D + 1);
+    std::fill(out, out + ds_records(batch, kv_heads, splits), (uint64_t)0);
+    std::vector<uint64_t> vz;
+    std::vector<unsigned char> column;
+    std::vector<signed char> value, t;
+    for (int item = 0; item < batch * kv_heads; ++item) {
+        const int b = item / kv_heads, hk = item % kv_heads, len = lens[b];
+        vz.resize((size_t)len);
+        column.resize((size_t)len * 4);
+        value.resize((size_t)len * 4);
+        t.resize((size_t)len);
+        int u[AS_D];
+        for (int c = 0; c < AS_D; ++c) u[c] = as_ternary(at.u + (uint64_t)item * AS_D + (uint64_t)c);
+        for (int j = 0; j < len; ++j) {
+            const uint64_t row = (uint64_t)item * n_k + (uint64_t)j;
+            uint64_t sum = 0;
+            for (int c = 0; c < AS_D; ++c)
+                sum += z[c] * (uint64_t)(int64_t)as_ternary(at.v + row * AS_D + (uint64_t)c);
+            vz[(size_t)j] = sum;
+            for (int quarter = 0; quarter < 4; ++quarter) {
+                int col, val;
+                as_e(at.e + row * 4 + (uint64_t)quarter, &col, &val);
+                column[(size_t)(4 * j + quarter)] = (unsigned char)(32 * quarter + col);
+                value[(size_t)(4 * j + quarter)] = (signed char)val;
+            }
+        }
+        for (int r = 0; r < group; ++r) {
+            const uint64_t h = (uint64_t)b * heads + (uint64_t)(hk * group + r);
+            signed char sign[AS_D];
+            int common = 0;
+            for (int c = 0; c < AS_D; ++c) {
+                const unsigned bits = as_q_bits(at.q + h * 8 + (uint64_t)(c / 16));
+                sign[c] = (bits >> (c % 16) & 1) ? 1 : -1;
+                common += sign[c] * u[c];
+            }
+            for (int j = 0; j < len; ++j) {
+                const unsigned char* const col = &column[(size_t)(4 * j)];
+                const signed char* const val = &value[(size_t)(4 * j)];
+                t[(size_t)j] = (signed char)(val[0] * sign[col[0]] + val[1] * sign[col[1]] +
+                                             val[2] * sign[col[2]] + val[3] * sign[col[3]]);
+            }
+            const uint64_t weight = as_weight(at.w + AS_WEIGHTS + h);
+            // the state over tiles first, first + stride, ... below last
+            auto state = [&](uint32_t first, uint32_t last, uint32_t stride) -> uint64_t {
+                if (first >= last) return 0;
+                int top = -4;
+                for (uint32_t tile = first; tile < last; tile += stride)
+                    for (int j = (int)tile * DS_TILE; j < std::min(len, (int)(tile + 1) * DS_TILE); ++j)
+                        top = std::max(top, (int)t[(size_t)j]);
+                uint64_t l256 = 0, o256 = 0;
+                for (uint32_t tile = first; tile < last; tile += stride)
+                    for (int j = (int)tile * DS_TILE; j < std::min(len, (int)(tile + 1) * DS_TILE); ++j) {
+                        const uint64_t p256 = (uint64_t)1 << (8 + t[(size_t)j] - top);
+                        l256 += p256;
+                        o256 += p256 * vz[(size_t)j];
+                    }
+                return weight * ((uint64_t)reps * (o256 + wa * l256) +
+                                 wb * (uint64_t)(int64_t)(common + top));
+            };
+            for (int s = 0; s < splits; ++s) {
+                uint32_t lo, hi;
+                ds_split_range((uint32_t)len, (uint32_t)s, (uint32_t)splits, &lo, &hi);
+                for (uint32_t w = 0; w < MS_WAVES_PER_WG; ++w)
+                    out[((long long)item * splits + s) * MS_WAVES_PER_WG + w] +=
+                        state(lo + w, hi, MS_WAVES_PER_WG);
+            }
+            out[finals + item] += state(0, ((uint32_t)len + DS_TILE - 1) / DS_TILE, 1);
+        }
+    }
+}
+
+// What 0 means for splits: enough workgroups for about two per CU, but no more
+// splits than a full-length sequence has tiles.
+extern "C" int na_decode_splits(int dev, int batch, int kv_heads, int max_pages, int* splits) {
+    if (batch < 1 || kv_heads < 1 || max_pages < 1 || splits == nullptr)
+        return arg_error("na_decode_splits: need batch, kv_heads and max_pages >= 1 (got %d, %d, "
+                         "%d) and a result pointer",
+                         batch, kv_heads, max_pages);
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    const long long items = (long long)batch * kv_heads;
+    const long long want = (2LL * prop.multiProcessorCount + items - 1) / items;
+    const long long tiles = ((long long)max_pages * DS_PAGE + DS_TILE - 1) / DS_TILE;
+    *splits = (int)std::max(1LL, std::min({want, tiles, (long long)NA_DECODE_MAX_SPLITS}));
+    return NA_OK;
+}
+
+// Pure host code: all batch * kv_heads * (4 splits + 1) checksums, n_out exactly
+// that.
+extern "C" int na_decode_sweep_expected(unsigned long long seed, int batch, int heads,
+                                        int kv_heads, int max_pages, const int* lens, int splits,
+                                        int reps, uint64_t* checksums, long long n_out) {
+    if (!ds_shape_ok(batch, heads, kv_heads, max_pages, splits, reps) || lens == nullptr ||
+        checksums == nullptr || n_out != ds_records(batch, kv_heads, splits))
+        return arg_error("na_decode_sweep_expected: need " DS_SHAPE_WORDS
+                         ", lengths and room for exactly 4 * splits + 1 checksums per (sequence, "
+                         "KV head) (checksums %p, n_out %lld)",
+                         DS_SHAPE_ARGS(batch, heads, kv_heads, max_pages, splits, reps),
+                         (void*)checksums, n_out);
+    const int bad = ds_bad_length(lens, batch, max_pages, reps);
+    if (bad >= 0)
+        return arg_error("na_decode_sweep_expected: need " DS_LENGTH_WORDS
+                         " (sequence %d has %d, max_pages %d, reps %d)",
+                         bad, lens[bad], max_pages, reps);
+    ds_expected(seed * MS_G, batch, heads, kv_heads, max_pages, lens, splits, reps, checksums);
+    return NA_OK;
+}
+
+// Writes the sweep's q, the paged K and V with their poison page and NaN tails,
+// the block table and the device copy of the lengths into caller-owned device
+// memory: k_cache and v_cache hold batch * max_pages + 1 pages.
+extern "C" int na_decode_sweep_fill(int dev, void* q, void* k_cache, void* v_cache,
+                                    void* block_table, void* seq_lens, int batch, int heads,
+                                    int kv_heads, int max_pages, const int* lens,
+                                    unsigned long long seed) {
+    if (!ds_shape_ok(batch, heads, kv_heads, max_pages, 1, 1) || lens == nullptr)
+        return arg_error("na_decode_sweep_fill: need " DS_SHAPE_WORDS " and lengths",
+                         DS_SHAPE_ARGS(batch, heads, kv_heads, max_pages, 1, 1));
+    const int bad = ds_bad_length(lens, batch, max_pages, 1);
+    if (bad >= 0)
+        return arg_error("na_decode_sweep_fill: need " DS_LENGTH_WORDS
+                         " (sequence %d has %d, max_pages %d)",
+                         bad, lens[bad], max_pages);
+    if (q == nullptr || k_cache == nullptr || v_cache == nullptr || block_table == nullptr ||
+        seq_lens == nullptr ||
+        (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) != 0 ||
+        (((uintptr_t)block_table | (uintptr_t)seq_lens) & 3) != 0)
+        return arg_error("na_decode_sweep_fill: need 16-byte aligned q, k_cache and v_cache (got "
+                         "%p, %p, %p) and 4-byte aligned block_table and seq_lens (%p, %p)",
+                         q, k_cache, v_cache, block_table, seq_lens);
+    HIP_CHECK(hipSetDevice(dev));
+    HIP_CHECK(hipMemcpy(seq_lens, lens, (size_t)batch * sizeof(int), hipMemcpyHostToDevice));
+    const uint64_t base = seed * MS_G, slots = (uint64_t)batch * (uint64_t)max_pages;
+    const uint64_t page_vecs = (uint64_t)kv_heads * DS_PAGE_VECS;
+    const uint64_t threads = (uint64_t)batch * heads * AS_ROW_VECS + 2 * (slots + 1) * page_vecs +
+                             slots;
+    ds_launch_fill((unsigned)((threads + MS_BLOCK - 1) / MS_BLOCK), static_cast<mt_vec*>(q),
+                   static_cast<mt_vec*>(k_cache), static_cast<mt_vec*>(v_cache),
+                   static_cast<int*>(block_table), static_cast<const int*>(seq_lens),
+                   (uint32_t)batch, (uint32_t)heads, (uint32_t)kv_heads, (uint32_t)max_pages,
+                   ds_paging_of(base, slots),
+                   as_layout_of(base, (uint64_t)batch * heads, (uint64_t)batch * kv_heads, 1,
+                                (uint64_t)max_pages * DS_PAGE));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// One HIP-event timed decode attention on caller-owned device tensors: the
+// sweep kernel on batch * kv_heads * splits workgroups and, for splits > 1, the
+// combine kernel behind it (the workspace between them is the library's). o,
+// when not null, receives the output; records receives the batch * kv_heads *
+// (4 splits + 1) records, whose checksums match na_decode_sweep_expected when
+// the tensors are na_decode_sweep_fill's of the same seed and shape and
+// scale_log2 is 1. Argument errors are detected before any HIP call.
+extern "C" int na_decode_run(int dev, const void* q, const void* k_cache, const void* v_cache,
+                             const void* block_table, const void* seq_lens, void* o, int batch,
+                             int heads, int kv_heads, int max_pages, long long num_pages,
+                             int splits, float scale_log2, int reps, unsigned long long seed,
+                             na_mfma_record* records, long long n_out, double* ms) {
+    if (!ds_shape_ok(batch, heads, kv_heads, max_pages, splits, reps) || num_pages < 1 ||
+        num_pages > INT32_MAX)
+        return arg_error("na_decode_run: need " DS_SHAPE_WORDS " and num_pages in 1..2^31-1 (got "
+                         "%lld)",
+                         DS_SHAPE_ARGS(batch, heads, kv_heads, max_pages, splits, reps), num_pages);
+    if (q == nullptr || k_cache == nullptr || v_cache == nullptr || block_table == nullptr ||
+        seq_lens == nullptr ||
+        (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)o) & 15) != 0 ||
+        (((uintptr_t)block_table | (uintptr_t)seq_lens) & 3) != 0)
+        return arg_error("na_decode_run: need 16-byte aligned q, k_cache, v_cache and o or a null "
+                         "o (got %p, %p, %p, %p) and 4-byte aligned block_table and seq_lens (%p, "
+                         "%p)",
+                         q, k_cache, v_cache, o, block_table, seq_lens);
+    if (!(scale_log2 > 0.f) || !std::isfinite(scale_log2))
+        return arg_error("na_decode_run: need a finite scale_log2 > 0 (got %g)",
+                         (double)scale_log2);
+    if (records == nullptr || n_out != ds_records(batch, kv_heads, splits))
+        return arg_error("na_decode_run: need room for exactly 4 * splits + 1 records per "
+                         "(sequence, KV head) (records %p, n_out %lld, want %lld)",
+                         (void*)records, n_out, ds_records(batch, kv_heads, splits));
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<float> workspace;
+    if (splits > 1) HIP_CHECK(workspace.alloc((size_t)batch * kv_heads * splits * DS_STATE));
+    const as_layout at = as_layout_of(seed * MS_G, (uint64_t)batch * heads,
+                                      (uint64_t)batch * kv_heads, 1, (uint64_t)max_pages * DS_PAGE);
+    return sweep_launch(dev, (size_t)n_out, records, ms, [&](na_mfma_record* recs) {
+        ds_launch_sweep(recs, static_cast<const mt_vec*>(q), static_cast<const mt_vec*>(k_cache),
+                        static_cast<const mt_vec*>(v_cache), static_cast<const int*>(block_table),
+                        static_cast<const int*>(seq_lens), static_cast<float*>(o), workspace.p,
+                        (uint32_t)batch, (uint32_t)heads, (uint32_t)kv_heads, (uint32_t)max_pages,
+                        (uint32_t)num_pages, (uint32_t)splits, scale_log2, (uint32_t)reps, at.w);
+        if (splits > 1)
+            ds_launch_combine(recs, workspace.p, static_cast<float*>(o), (uint32_t)batch,
+                              (uint32_t)heads, (uint32_t)kv_heads, (uint32_t)splits, scale_log2,
+                              at.w);
+    });
+}
+
+// Pure host code. Returns NA_ERR_VERIFY on any bad record (ms_tally's rules),
+// with a message that names the first by sequence, KV head, split and wave, or
+// as the final state of its (sequence, KV head); *res is filled either way.
+extern "C" int na_decode_sweep_verify(const na_mfma_record* recs, long long n, int batch,
+                                      int heads, int kv_heads, int max_pages, const int* lens,
+                                      int splits, int reps, unsigned long long seed,
+                                      na_mfma_sweep_result* res) {
+    if (!ds_shape_ok(batch, heads, kv_heads, max_pages, splits, reps) || lens == nullptr ||
+        recs == nullptr || n != ds_records(batch, kv_heads, splits) || res == nullptr)
+        return arg_error("na_decode_sweep_verify: need " DS_SHAPE_WORDS
+                         ", lengths, exactly 4 * splits + 1 records per (sequence, KV head) (recs "
+                         "%p, n %lld) and a result pointer",
+                         DS_SHAPE_ARGS(batch, heads, kv_heads, max_pages, splits, reps),
+                         (const void*)recs, n);
+    const int bad = ds_bad_length(lens, batch, max_pages, reps);
+    if (bad >= 0)
+        return arg_error("na_decode_sweep_verify: need " DS_LENGTH_WORDS
+                         " (sequence %d has %d, max_pages %d, reps %d)",
+                         bad, lens[bad], max_pages, reps);
+    std::vector<uint64_t> want((size_t)n);
+    ds_expected(seed * MS_G, batch, heads, kv_heads, max_pages, lens, splits, reps, want.data());
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const long long w = (long long)res->first_bad_wave;
+    const long long finals = (long long)batch * kv_heads * splits * MS_WAVES_PER_WG;
+    char what[96];
+    if (w < finals) {
+        const long long item = w / MS_WAVES_PER_WG / splits;
+        std::snprintf(what, sizeof(what), "sequence %lld KV head %lld split %lld wave %lld",
+                      item / kv_heads, item % kv_heads, w / MS_WAVES_PER_WG % splits,
+                      w % MS_WAVES_PER_WG);
+    } else {
+        std::snprintf(what, sizeof(what), "final state of sequence %lld KV head %lld",
+                      (w - finals) / kv_heads, (w - finals) % kv_heads);
+    }
+    return na_error(NA_ERR_VERIFY,
+                    "decode sweep: %llu of %llu records wrong on %llu CU(s), first record %lld "
+                    "(%s) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, what, u[0], u[1], u[2], u[3], u[4]);
+}
+
+// Whole sweep on tensors the agent allocates and fills itself: one untimed
+// warm-up launch, the timed launch, the verify. 0 = default for batch (64),
+// heads (32), kv_heads (heads / 8, or heads when 8 does not divide them),
+// max_pages (512), splits (na_decode_splits) and reps (the most the bound
+// allows at 16 max_pages tokens). Sequence b is (16 max_pages) / 4 + mix64(seed
+// G - 2 - b) % (16 max_pages - (16 max_pages) / 4 + 1) tokens long, at least 1.
+// *gbps counts the 512 bytes of K and V per token, KV head and repetition over
+// the event time.
+extern "C" int na_decode_sweep(int dev, int batch, int heads, int kv_heads, int max_pages,
+                               int splits, int reps, unsigned long long seed,
+                               na_mfma_sweep_result* res, double* gbps) {
+    if (res == nullptr || batch < 0 || heads < 0 || kv_heads < 0 || max_pages < 0 || splits < 0 ||
+        reps < 0)
+        return arg_error("na_decode_sweep: need batch, heads, kv_heads, max_pages, splits and reps "
+                         ">= 0 (got %d, %d, %d, %d, %d, %d) and a result pointer",
+                         batch, heads, kv_heads, max_pages, splits, reps);
+    if (batch == 0) batch = NA_DECODE_DEFAULT_BATCH;
+    if (heads == 0) heads = NA_DECODE_DEFAULT_HEADS;
+    if (kv_heads == 0) kv_heads = heads % 8 == 0 ? heads / 8 : heads;
+    if (max_pages == 0) max_pages = NA_DECODE_DEFAULT_PAGES;
+    if (max_pages > NA_DECODE_MAX_PAGES)
+        return arg_error("na_decode_sweep: need max_pages <= %d (got %d)", NA_DECODE_MAX_PAGES,
+                         max_pages);
+    const int longest = DS_PAGE * max_pages;
+    if (reps == 0) reps = std::max(1, (NA_DECODE_EXACT - 1) / (256 * longest));
+    if (splits == 0) {
+        const int rc = na_decode_splits(dev, batch, kv_heads, max_pages, &splits);
+        if (rc != NA_OK) return rc;
+    }
+    if (!ds_shape_ok(batch, heads, kv_heads, max_pages, splits, reps) ||
+        256LL * reps * longest >= NA_DECODE_EXACT)
+        return arg_error("na_decode_sweep: need " DS_SHAPE_WORDS
+                         " and 256 * reps * 16 * max_pages < 2^24",
+                         DS_SHAPE_ARGS(batch, heads, kv_heads, max_pages, splits, reps));
+    std::vector<int> lens((size_t)batch);
+    double tokens = 0.0;
+    for (int b = 0; b < batch; ++b) {
+        const uint64_t span = (uint64_t)(longest - longest / 4 + 1);
+        lens[(size_t)b] = std::max(1, longest / 4 + (int)(mt_mix64(seed * MS_G - 2 - (uint64_t)b) % span));
+        tokens += lens[(size_t)b];
+    }
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t num_pages = (size_t)batch * (size_t)max_pages + 1;
+    const size_t cache_bytes = num_pages * (size_t)kv_heads * DS_PAGE * AS_D * 2;
+    dev_buf<unsigned char> q, k, v;
+    dev_buf<int> table, dlens;
+    HIP_CHECK(q.alloc((size_t)batch * (size_t)heads * AS_D * 2));
+    HIP_CHECK(k.alloc(cache_bytes));
+    HIP_CHECK(v.alloc(cache_bytes));
+    HIP_CHECK(table.alloc((size_t)batch * (size_t)max_pages));
+    HIP_CHECK(dlens.alloc((size_t)batch));
+    int rc = na_decode_sweep_fill(dev, q.p, k.p, v.p, table.p, dlens.p, batch, heads, kv_heads,
+                                  max_pages, lens.data(), seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs((size_t)ds_records(batch, kv_heads, splits));
+    double ms = 0.0;
+    rc = sweep_twice([&] {
+        return na_decode_run(dev, q.p, k.p, v.p, table.p, dlens.p, nullptr, batch, heads, kv_heads,
+                             max_pages, (long long)num_pages, splits, 1.0f, reps, seed,
+                             recs.data(), (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
+    if (gbps) *gbps = tokens * kv_heads * (2.0 * AS_D * 2) * reps / (ms * 1e6);
+    return na_decode_sweep_verify(recs.data(), (long long)recs.size(), batch, heads, kv_heads,
+                                  max_pages, lens.data(), splits, reps, seed, res);
 }

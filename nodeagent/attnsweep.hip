@@ -10,8 +10,12 @@
 // (valusweep.h issues v_pk_fma_f32 on purpose, which is why the flag cannot go
 // on agent.hip as a whole).
 
+// The decode attention sweep's kernels (decodesweep.h) are built here too, for
+// the same reason: its merges and rescales are claimed exact.
+
 #define AS_KERNELS
 #include "attnsweep.h"
+#include "decodesweep.h"
 
 void as_launch_fill(unsigned grid, mt_vec* q, mt_vec* k, mt_vec* v, mt_u64 q_vecs, mt_u64 kv_vecs,
                     mt_u64 n_k, as_layout at) {
@@ -23,4 +27,26 @@ void as_launch_sweep(na_mfma_record* records, const mt_vec* q, const mt_vec* k, 
                      uint32_t causal, float c, uint32_t reps, mt_u64 wbase) {
     attn_sweep_kernel<<<dim3(heads * nqb), dim3(MS_BLOCK), AS_LDS_BYTES>>>(
         records, q, k, v, o, heads, group, nqb, nkt, causal, c, reps, wbase);
+}
+
+void ds_launch_fill(unsigned grid, mt_vec* q, mt_vec* k, mt_vec* v, int* table, const int* lens,
+                    uint32_t batch, uint32_t heads, uint32_t kv_heads, uint32_t max_pages,
+                    ds_paging pg, as_layout at) {
+    decode_fill_kernel<<<dim3(grid), dim3(MS_BLOCK)>>>(q, k, v, table, lens, batch, heads,
+                                                       kv_heads, max_pages, pg, at);
+}
+
+void ds_launch_sweep(na_mfma_record* records, const mt_vec* q, const mt_vec* k, const mt_vec* v,
+                     const int* table, const int* lens, float* o, float* workspace,
+                     uint32_t batch, uint32_t heads, uint32_t kv_heads, uint32_t max_pages,
+                     uint32_t num_pages, uint32_t splits, float c, uint32_t reps, mt_u64 wbase) {
+    decode_sweep_kernel<<<dim3(batch * kv_heads * splits), dim3(MS_BLOCK)>>>(
+        records, q, k, v, table, lens, o, workspace, batch, heads, kv_heads, max_pages, num_pages,
+        splits, c, reps, wbase);
+}
+
+void ds_launch_combine(na_mfma_record* records, const float* workspace, float* o, uint32_t batch,
+                       uint32_t heads, uint32_t kv_heads, uint32_t splits, float c, mt_u64 wbase) {
+    decode_combine_kernel<<<dim3(batch * kv_heads), dim3(MS_BLOCK)>>>(
+        records, workspace, o, batch, heads, kv_heads, splits, c, wbase);
 }

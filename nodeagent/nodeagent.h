@@ -57,6 +57,14 @@
 #define NA_ATTN_MAX_HEADS 4096   // with at most this many heads
 #define NA_ATTN_MAX_Q (1 << 20)  // of at most this many queries,
 #define NA_ATTN_EXACT (1 << 24)  // and 256 * reps * n_k stays under this: exact f32 sums
+#define NA_DECODE_HEAD_DIM 128   // the decode attention sweep's head dimension;
+#define NA_DECODE_PAGE 16        // tokens in a page of its KV cache;
+#define NA_DECODE_MAX_GROUP 16   // heads / kv_heads is at most this,
+#define NA_DECODE_MAX_BATCH 4096     // with at most this many sequences
+#define NA_DECODE_MAX_HEADS 1024     // of at most this many heads
+#define NA_DECODE_MAX_PAGES (1 << 16)  // and pages in a row of the block table,
+#define NA_DECODE_MAX_SPLITS 64  // at most this many workgroups share a (sequence, KV head),
+#define NA_DECODE_EXACT (1 << 24)  // and 256 * reps * the longest length stays under this
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -74,7 +82,11 @@
 // workgroup, `wave` being 4 * workgroup + wave and the clocks around the passes.
 // The attention sweep (attnsweep.h) leaves it for each wave of each block of
 // 128 queries of each head, `wave` being 4 * (head * n_q / 128 + block) + wave
-// and the clocks around the walk over the keys.
+// and the clocks around the walk over the keys. The decode attention sweep
+// (decodesweep.h) leaves it for each wave of each split of each (sequence, KV
+// head), `wave` being 4 * ((b * kv_heads + hk) * splits + split) + wave, and
+// after those one per (sequence, KV head) over the merged state, `wave` being 4
+// * batch * kv_heads * splits + b * kv_heads + hk.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -381,6 +393,35 @@ int na_attn_sweep_verify(const na_mfma_record* recs, long long n, int heads, int
                          unsigned long long seed, na_mfma_sweep_result* res);
 int na_attn_sweep(int dev, int heads, int kv_heads, long long n_q, long long n_k, int causal,
                   int reps, unsigned long long seed, na_mfma_sweep_result* res, double* tflops);
+
+// chip-wide paged decode attention sweep, and the decode attention it runs as
+// an operation on caller-owned tensors: one query token per sequence against a
+// KV cache in pages of 16 tokens. q is bf16[batch][heads][128], k_cache and
+// v_cache bf16[num_pages][kv_heads][16][128], block_table int32[batch][max_pages]
+// and seq_lens int32[batch] in device memory (each length 1 .. 16 * max_pages), o
+// null or float[batch][heads][128]; heads a multiple of kv_heads with heads /
+// kv_heads <= 16; splits workgroups share one (sequence, KV head); reps and
+// scale_log2 as na_attn_run's; `lens` is the host's copy of the lengths;
+// operands, paging and checksums in decodesweep.h; batch * kv_heads * (4 * splits
+// + 1) records, results are the matrix-core sweep's. na_decode_splits gives the
+// splits that na_decode_sweep takes for splits = 0.
+int na_decode_splits(int dev, int batch, int kv_heads, int max_pages, int* splits);
+int na_decode_sweep_fill(int dev, void* q, void* k_cache, void* v_cache, void* block_table,
+                         void* seq_lens, int batch, int heads, int kv_heads, int max_pages,
+                         const int* lens, unsigned long long seed);
+int na_decode_sweep_expected(unsigned long long seed, int batch, int heads, int kv_heads,
+                             int max_pages, const int* lens, int splits, int reps,
+                             uint64_t* checksums, long long n_out);
+int na_decode_run(int dev, const void* q, const void* k_cache, const void* v_cache,
+                  const void* block_table, const void* seq_lens, void* o, int batch, int heads,
+                  int kv_heads, int max_pages, long long num_pages, int splits, float scale_log2,
+                  int reps, unsigned long long seed, na_mfma_record* records, long long n_out,
+                  double* ms);
+int na_decode_sweep_verify(const na_mfma_record* recs, long long n, int batch, int heads,
+                           int kv_heads, int max_pages, const int* lens, int splits, int reps,
+                           unsigned long long seed, na_mfma_sweep_result* res);
+int na_decode_sweep(int dev, int batch, int heads, int kv_heads, int max_pages, int splits,
+                    int reps, unsigned long long seed, na_mfma_sweep_result* res, double* gbps);
 
 #ifdef __cplusplus
 }
