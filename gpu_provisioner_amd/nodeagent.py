@@ -8,7 +8,7 @@ there is no eager/python fallback for the hardware checks.
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
 [--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]
-[--mxquant-sweep] [--attn-sweep] [--decode-sweep]``
+[--mxquant-sweep] [--attn-sweep] [--decode-sweep] [--moe-gemm-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -265,6 +265,26 @@ DECODE_MAX_SPLITS = 64
 # rule of the floors above. The device-to-device spread has not been measured;
 # 0.70 is borrowed from the MFMA floor. 0 disables the floor.
 MIN_DECODE_SWEEP_GBPS = 3870.7
+
+# Chip-wide MoE grouped GEMM sweep (nodeagent/moegemmsweep.h): the expert GEMM
+# of a mixture-of-experts layer, C[s] = reps * X[row_ids[s]] * W[e]^T for the
+# slots s of expert e: rows gathered through an index array, a ragged count per
+# expert, tiles of 128 slots x 256 columns found on the device from the offsets.
+# Also an operation on caller-owned tensors (``moe_gemm_run``). The default seed
+# is "MI355XMO"; ``4 * moe_gemm_tiles(...)`` records, results are the
+# matrix-core sweep's.
+DEFAULT_MOE_GEMM_SWEEP_SEED = 0x4D493335_35584D4F
+# nodeagent/nodeagent.h: NA_MOE_TILE_M, NA_MOE_TILE_N, NA_MOE_MAX_EXPERTS
+MOE_TILE_M = 128  # slots in a tile; a tile has one expert
+MOE_TILE_N = 256  # n is a multiple of this
+MOE_MAX_EXPERTS = 256
+# Floor of the default sweep (8192 tokens top-4 on 32 experts of N = 2048, K =
+# 1024, hashed ragged counts) over the valid rows, bf16: 0.70 x the 515.0 TFLOP/s median of
+# five processes on MI355X (profiles/moe_gemm_sweep_mi355x.txt), the rule of the
+# floors above, with the GEMM floor's caveat: small integers clock higher than
+# random data. The device-to-device spread of this kernel has not been
+# measured; 0.70 is borrowed from the MFMA floor. 0 disables the floor.
+MIN_MOE_GEMM_SWEEP_TFLOPS = 360.5
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -556,6 +576,43 @@ class DecodeSweepResult:
             what = f"final state of sequence {(w - finals) // kv} KV head {(w - finals) % kv}"
         return (
             f"{self.sweep.describe()}; first record {w} ({what}) on "
+            f"{mfma_unit_name(self.sweep.bad_simds[0])}"
+        )
+
+
+@dataclass
+class MoeGemmSweepResult:
+    """Outcome of a MoE grouped GEMM sweep verify: the matrix-core sweep's
+    result over the 4 records of every workgroup of the launch bound (tiles
+    first, idle records behind them), and the rate of the timed launch over
+    the valid rows (0 when only a verify was done). ``counts`` are the slots
+    per expert where the caller knows them."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    n: int = 0
+    counts: tuple = ()
+    tflops: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong record by expert, row tile
+        and sub-tile (by tile, without the counts) and unit."""
+        w, nt = self.sweep.first_bad_wave, max(self.n // MOE_TILE_N, 1)
+        what, row_tile = f"tile {w // 4}", w // 4 // nt
+        for e, count in enumerate(self.counts):
+            mine = -(-count // MOE_TILE_M)
+            if row_tile < mine:
+                what = f"expert {e} row tile {row_tile} column tile {w // 4 % nt}"
+                break
+            row_tile -= mine
+        else:
+            if self.counts:
+                what = "a surplus workgroup that must report idle"
+        return (
+            f"{self.sweep.describe()}; first record {w} ({what} sub-tile {w >> 1 & 1},{w & 1}) on "
             f"{mfma_unit_name(self.sweep.bad_simds[0])}"
         )
 
@@ -948,6 +1005,21 @@ _ABI = {
                _P(_MfmaSweepResultC))),
     "na_decode_sweep": (
         _int, (_int, _int, _int, _int, _int, _int, _int, _u64, _P(_MfmaSweepResultC), _double_p)),
+    "na_moe_gemm_tiles": (_int, (_i64, _int, _i64, _i64_p)),
+    "na_moe_gemm_fill": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _void_p, _i64, _i64, _int, _i64, _i64,
+               _int_p, _u64)),
+    "na_moe_gemm_expected": (
+        _int, (_u64, _i64, _i64, _int, _i64, _i64, _int_p, _int, _u64_p, _i64)),
+    "na_moe_gemm_run": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _void_p, _void_p, _i64, _i64, _int, _i64,
+               _i64, _int, _u64, _P(MfmaRecord), _i64, _double_p)),
+    "na_moe_gemm_verify": (
+        _int, (_P(MfmaRecord), _i64, _i64, _i64, _int, _i64, _i64, _int_p, _int, _u64,
+               _P(_MfmaSweepResultC))),
+    "na_moe_gemm_sweep": (
+        _int, (_int, _int, _i64, _i64, _int, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC),
+               _double_p)),
 }
 
 
@@ -1038,6 +1110,12 @@ class GPUReport:
     decode_sweep_clock_mhz: float = 0.0  # informational, no floor
     decode_sweep_units_seen: int = 0
     decode_sweep_bad_waves: int = 0  # wave records and final records
+    # chip-wide MoE grouped GEMM sweep (opt-in)
+    moe_gemm_sweep_tflops: float = 0.0  # over the valid rows
+    moe_gemm_sweep_clock_mhz: float = 0.0  # informational, no floor
+    moe_gemm_sweep_units_seen: int = 0
+    moe_gemm_sweep_bad_waves: int = 0  # tile records and idle records
+    moe_gemm_sweep_skipped: str = ""  # reason, when requested but not run
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -2271,6 +2349,119 @@ class NodeAgent:
         if not res.ok:
             g.problems.append(f"decode attention sweep: {res.describe()}")
 
+    # -- chip-wide MoE grouped GEMM sweep -------------------------------------------
+
+    def moe_gemm_tiles(self, slots: int, experts: int, n: int) -> int:
+        """The workgroups a launch takes, ``(slots // 128 + experts) * n //
+        256``: an upper bound of the tiles, which only the device knows. A
+        launch leaves 4 records for each. Needs no GPU."""
+        out = ctypes.c_longlong(0)
+        self._check(self.lib.na_moe_gemm_tiles(slots, experts, n, ctypes.byref(out)),
+                    "moe_gemm_tiles")
+        return out.value
+
+    def moe_gemm_fill(self, dev: int, x: int, w: int, row_ids: int, offsets: int, tokens: int,
+                      slots: int, n: int, k: int, counts,
+                      seed: int = DEFAULT_MOE_GEMM_SWEEP_SEED, dtype: str = "bf16") -> None:
+        """Write the sweep's hashed X (``tokens`` x ``k``) and W (``len(counts)``
+        x ``n`` x ``k``) in ``dtype``, the hashed int32 ``row_ids[slots]`` and
+        the prefix sums of ``counts`` as int32 ``offsets`` into device memory
+        the caller owns (device pointers as integers)."""
+        rc = self.lib.na_moe_gemm_fill(dev, self._matrix_code("mfma", dtype), x, w, row_ids,
+                                       offsets, tokens, slots, len(counts), n, k,
+                                       (ctypes.c_int * len(counts))(*counts), seed)
+        self._check(rc, f"moe_gemm_fill({dev})")
+
+    def moe_gemm_expected(self, tokens: int, slots: int, n: int, k: int, counts, reps: int = 1,
+                          seed: int = DEFAULT_MOE_GEMM_SWEEP_SEED) -> list:
+        """Reference checksums of every record of a launch on ``moe_gemm_fill``'s
+        tensors: ``4 * tile + 2 * wr + wc`` over the valid rows of each
+        sub-tile, tiles by expert, row tile and column tile, then 0 for the idle
+        records; the same for both dtypes. Host arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * (4 * self.moe_gemm_tiles(slots, len(counts), n)))()
+        rc = self.lib.na_moe_gemm_expected(seed, tokens, slots, len(counts), n, k,
+                                           (ctypes.c_int * len(counts))(*counts), reps, out,
+                                           len(out))
+        self._check(rc, "moe_gemm_expected")
+        return list(out)
+
+    def moe_gemm_run(self, dev: int, x: int, w: int, row_ids: int, offsets: int, tokens: int,
+                     slots: int, experts: int, n: int, k: int, reps: int = 1,
+                     seed: int = DEFAULT_MOE_GEMM_SWEEP_SEED, dtype: str = "bf16",
+                     c: int = 0) -> tuple:
+        """One launch of the expert GEMM ``C[s] = reps * X[row_ids[s]] *
+        W[e]^T`` for the slots ``offsets[e] <= s < offsets[e + 1]``, all device
+        memory: ``x`` is ``tokens`` x ``k`` and ``w`` ``experts`` x ``n`` x
+        ``k`` in ``dtype``, ``row_ids`` int32 ``[slots]``, ``offsets`` int32
+        ``[experts + 1]``. ``c``, when not 0, is device memory for the ``slots``
+        x ``n`` float32 result; rows from ``offsets[experts]`` on are not
+        written. Returns ``(records, ms)``."""
+        recs = (MfmaRecord * (4 * self.moe_gemm_tiles(slots, experts, n)))()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_moe_gemm_run(dev, self._matrix_code("mfma", dtype), x, w, row_ids,
+                                      offsets, c or None, tokens, slots, experts, n, k, reps, seed,
+                                      recs, len(recs), ctypes.byref(ms))
+        self._check(rc, f"moe_gemm_run({dev})")
+        return recs, ms.value
+
+    def moe_gemm_verify(self, recs, tokens: int, slots: int, n: int, k: int, counts,
+                        reps: int = 1, seed: int = DEFAULT_MOE_GEMM_SWEEP_SEED,
+                        dtype: str = "bf16") -> tuple:
+        """Compare every record against the host reference of ``moe_gemm_fill``'s
+        tensors: the tiles' checksums, and that exactly the records behind them
+        are idle. Returns ``(rc, MoeGemmSweepResult)``; rc is ``NA_ERR_VERIFY``
+        on any bad record, and ``na_last_error`` then names the first by unit,
+        expert, row tile and sub-tile."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_moe_gemm_verify(recs, len(recs), tokens, slots, len(counts), n, k,
+                                         (ctypes.c_int * len(counts))(*counts), reps, seed,
+                                         ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, MoeGemmSweepResult()
+        return rc, MoeGemmSweepResult(MfmaSweepResult._from_c(dtype, res), n, tuple(counts))
+
+    def moe_gemm_sweep(self, dev: int, dtype: str = "bf16", tokens: int = 0, slots: int = 0,
+                       experts: int = 0, n: int = 0, k: int = 0, reps: int = 0,
+                       seed: int = DEFAULT_MOE_GEMM_SWEEP_SEED) -> MoeGemmSweepResult:
+        """Allocate and fill the tensors with ragged counts hashed from the
+        seed (empty experts, experts of one slot and dropped tokens among
+        them), run the expert GEMM twice (the second launch timed) and verify
+        every record bit-exactly. 0 selects the default: 8192 tokens, four
+        slots a token, 32 experts, ``n`` 2048, ``k`` 1024 and the ``reps`` of a
+        16-19 ms launch. Wrong records come back in the result (``.ok``
+        False), not as an exception; operands that do not fit in half of the
+        free device memory raise ``GemmSweepNoRoom``."""
+        res, tflops = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_moe_gemm_sweep(dev, self._matrix_code("mfma", dtype), tokens, slots,
+                                        experts, n, k, reps, seed, ctypes.byref(res),
+                                        ctypes.byref(tflops))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = GemmSweepNoRoom if "do not fit" in err else NodeAgentError
+            raise cls(f"moe_gemm_sweep({dev}): {err}")
+        return MoeGemmSweepResult(MfmaSweepResult._from_c(dtype, res, tflops.value), n or 2048,
+                                  (), tflops.value)
+
+    def _run_moe_gemm_sweep(self, g: GPUReport) -> None:
+        try:
+            res = self.moe_gemm_sweep(g.index)
+        except GemmSweepNoRoom as e:
+            # a busy GPU must not get its node replaced for lack of free memory
+            g.moe_gemm_sweep_skipped = str(e)
+            return
+        g.moe_gemm_sweep_tflops = round(res.tflops, 1)
+        g.moe_gemm_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+        g.moe_gemm_sweep_units_seen = res.sweep.units_seen
+        g.moe_gemm_sweep_bad_waves = res.sweep.bad_waves
+        if res.tflops < MIN_MOE_GEMM_SWEEP_TFLOPS:
+            g.problems.append(
+                f"MoE GEMM sweep {g.moe_gemm_sweep_tflops} TFLOP/s below floor "
+                f"{MIN_MOE_GEMM_SWEEP_TFLOPS}"
+            )
+        if not res.ok:
+            # the library's message names the expert: only it knows the sweep's counts
+            g.problems.append(f"MoE GEMM sweep: {res.describe()}; {self._err()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -2290,7 +2481,8 @@ class NodeAgent:
               valu_sweep: bool = False, cache_sweep: bool = False,
               load_sweep: bool = False, gemm_sweep: bool = False,
               mxgemm_sweep: bool = False, mxquant_sweep: bool = False,
-              attn_sweep: bool = False, decode_sweep: bool = False) -> NodeReport:
+              attn_sweep: bool = False, decode_sweep: bool = False,
+              moe_gemm_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -2382,7 +2574,16 @@ class NodeAgent:
         every merged state verified exactly. A wrong record is a problem that
         names its sequence, KV head, split, wave and unit, as is a rate of KV
         bytes under ``MIN_DECODE_SWEEP_GBPS``. False (default) makes no new
-        library call."""
+        library call.
+
+        ``moe_gemm_sweep`` additionally runs the chip-wide MoE grouped GEMM
+        sweep on every GPU: the bf16 expert GEMM on rows gathered through an
+        index array, ragged counts per expert, the tiles found on the device.
+        A wrong record is a problem that names its expert, row tile, sub-tile
+        and unit, as is a rate over the valid rows under
+        ``MIN_MOE_GEMM_SWEEP_TFLOPS``; operands that do not fit land in
+        ``moe_gemm_sweep_skipped``. False (default) makes no new library
+        call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
         if expect_gpus and report.gpu_count != expect_gpus:
@@ -2440,6 +2641,8 @@ class NodeAgent:
                     self._run_attn_sweep(g)
                 if decode_sweep:
                     self._run_decode_sweep(g)
+                if moe_gemm_sweep:
+                    self._run_moe_gemm_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -2643,6 +2846,17 @@ def main(argv=None) -> int:
         "KV bytes per second",
     )
     ap.add_argument(
+        "--moe-gemm-sweep",
+        action="store_true",
+        help="also run the chip-wide MoE grouped GEMM sweep on every GPU: the bf16 expert GEMM of "
+        "a mixture-of-experts layer on hashed small-integer operands, rows gathered through an "
+        "index array sorted by expert, ragged counts per expert (empty experts and experts of one "
+        "slot among them), tiles of 128 slots x 256 columns found by each workgroup from the "
+        "offsets in device memory; every wave's checksum over the valid rows of its sub-tile is "
+        "recomputed on the host and a wrong one attributed to its XCC/SE/SH/CU/SIMD, expert, row "
+        "tile and sub-tile; reports the rate over the valid rows",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -2667,6 +2881,7 @@ def main(argv=None) -> int:
             mxquant_sweep=args.mxquant_sweep,
             attn_sweep=args.attn_sweep,
             decode_sweep=args.decode_sweep,
+            moe_gemm_sweep=args.moe_gemm_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

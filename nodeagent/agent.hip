@@ -3987,3 +3987,358 @@ extern "C" int na_decode_sweep(int dev, int batch, int heads, int kv_heads, int 
     return na_decode_sweep_verify(recs.data(), (long long)recs.size(), batch, heads, kv_heads,
                                   max_pages, lens.data(), splits, reps, seed, res);
 }
+
+// ---------------------------------------------------------------------------
+// Chip-wide MoE grouped GEMM sweep (specification and kernels in
+// moegemmsweep.h, the kernels compiled in attnsweep.hip)
+// ---------------------------------------------------------------------------
+//
+// The expert GEMM of a mixture-of-experts layer: rows of X gathered through an
+// index array sorted by expert, a ragged count of rows per expert that only the
+// device knows, each expert's rows against that expert's weights. Tiles of 128
+// slots x 256 columns are found by every workgroup from the offsets in device
+// memory; the host launches an upper bound and expects the surplus workgroups
+// to report idle. As a sweep every wave's checksum over the valid rows of its
+// sub-tile is recomputed by the host exactly; as an operation (na_moe_gemm_run)
+// it takes any bf16 or E4M3 tensors.
+
+#include "moegemmsweep.h"
+
+// The whole sweep's shape: 8192 tokens routed top-4 to 32 experts of N = 2048,
+// K = 1024 (the host reference hashes slots * K + experts * N * K = 1.5 x 2^26
+// elements, which keeps the verify under 0.3 s), counts hashed from the seed
+// with empty experts, experts of one slot and dropped tokens among them.
+#define NA_MOE_DEFAULT_TOKENS 8192
+#define NA_MOE_DEFAULT_TOPK 4
+#define NA_MOE_DEFAULT_EXPERTS 32
+#define NA_MOE_DEFAULT_N 2048
+#define NA_MOE_DEFAULT_K 1024
+// Chosen on the MI355X for a launch of 16-19 ms: 0.229 ms (bf16) and 0.120 ms
+// (fp8) per repetition measured (profiles/moe_gemm_sweep_mi355x.txt);
+// 6 * reps * 1024 < 2^24 allows up to 2730.
+static const int mg_default_reps[2] = {72, 140};
+
+static bool mg_shape_ok(long long tokens, long long slots, int experts, long long n, long long k,
+                        int reps, long long bk) {
+    return tokens >= 1 && tokens <= NA_MOE_MAX_ROWS && slots >= 1 && slots <= NA_MOE_MAX_ROWS &&
+           experts >= 1 && experts <= NA_MOE_MAX_EXPERTS && n >= MG_TILE_N &&
+           n <= NA_GEMM_MAX_DIM && n % MG_TILE_N == 0 && k >= bk && k % bk == 0 && reps >= 1 &&
+           k < NA_GEMM_EXACT && 6 * (long long)reps * k < NA_GEMM_EXACT &&
+           (slots / MG_TILE_M + experts) * (n / MG_TILE_N) <= NA_MFMA_MAX_WORKGROUPS;
+}
+
+#define MG_SHAPE_WORDS                                                                          \
+    "tokens and slots in 1..%d (got %lld, %lld), experts in 1..%d (got %d), n_cols a multiple " \
+    "of %d up to %d (got %lld), k a positive multiple of %lld (got %lld), reps >= 1 and 6 * "   \
+    "reps * k < 2^24 (reps %d), at most %d workgroups"
+#define MG_SHAPE_ARGS(tokens, slots, experts, n, k, reps, bk)                                  \
+    NA_MOE_MAX_ROWS, (long long)(tokens), (long long)(slots), NA_MOE_MAX_EXPERTS, experts,     \
+        MG_TILE_N, NA_GEMM_MAX_DIM, (long long)(n), (long long)(bk), (long long)(k), reps,     \
+        NA_MFMA_MAX_WORKGROUPS
+
+static long long mg_bound(long long slots, int experts, long long n) {
+    return (long long)mg_row_tile_bound((uint32_t)slots, (uint32_t)experts) * (n / MG_TILE_N);
+}
+
+// The first expert whose count is negative or takes the sum past `slots`; -1
+// for none.
+static int mg_bad_count(const int* counts, int experts, long long slots) {
+    long long sum = 0;
+    for (int e = 0; e < experts; ++e)
+        if (counts[e] < 0 || (sum += counts[e]) > slots) return e;
+    return -1;
+}
+
+#define MG_COUNT_WORDS "every count >= 0 and their sum at most slots"
+
+// Pure host code; no HIP call.
+extern "C" int na_moe_gemm_tiles(long long slots, int experts, long long n_cols,
+                                 long long* bound) {
+    if (!mg_shape_ok(1, slots, experts, n_cols, NA_GEMM_BK_FP8, 1, NA_GEMM_BK_FP8) ||
+        bound == nullptr)
+        return arg_error("na_moe_gemm_tiles: need slots in 1..%d (got %lld), experts in 1..%d "
+                         "(got %d), n_cols a multiple of %d up to %d (got %lld), at most %d "
+                         "workgroups, and a result pointer",
+                         NA_MOE_MAX_ROWS, slots, NA_MOE_MAX_EXPERTS, experts, MG_TILE_N,
+                         NA_GEMM_MAX_DIM, n_cols, NA_MFMA_MAX_WORKGROUPS);
+    *bound = mg_bound(slots, experts, n_cols);
+    return NA_OK;
+}
+
+// Every record's checksum without O(slots N K) work, by the GEMM sweep's U/V
+// identity per (row tile, expert): the wave that owns valid slots R and columns
+// S of expert e has reps * sum_k U[k] * V[k] with U[k] = sum_{s in R} p_s
+// X[row_ids[s]][k] and V[k] = sum_{j in S} q_j W[e][j][k]. V is built once per
+// expert and 128-column block, U per half of a row tile: O(slots K + experts N
+// K) hashes. Records of no tile, and sub-tiles with no valid row, stay 0.
+static void mg_expected(uint64_t base, long long tokens, long long slots, int experts, long long n,
+                        long long k, const int* counts, int reps, uint64_t* out) {
+    const uint64_t wx = base + (uint64_t)tokens * (uint64_t)k;  // where W starts
+    const uint64_t wbase = wx + (uint64_t)experts * (uint64_t)n * (uint64_t)k;
+    const long long nt = n / MG_TILE_N;
+    std::fill(out, out + MS_WAVES_PER_WG * mg_bound(slots, experts, n), (uint64_t)0);
+    std::vector<uint64_t> u((size_t)(2 * k)), v((size_t)(2 * nt * k));
+    long long row_tile = 0, start = 0;
+    for (int e = 0; e < experts; start += counts[e], ++e) {
+        if (counts[e] == 0) continue;
+        std::fill(v.begin(), v.end(), (uint64_t)0);
+        for (long long j = 0; j < n; ++j) {
+            const uint64_t q = gs_weight(wbase + (uint64_t)(slots + j));
+            const uint64_t at = wx + (uint64_t)(((long long)e * n + j) * k);
+            uint64_t* const row = &v[(size_t)(j / (MG_TILE_N / 2) * k)];
+            for (long long kk = 0; kk < k; ++kk)
+                row[kk] += q * (uint64_t)(int64_t)gs_element(at + (uint64_t)kk, GS_MOD_B);
+        }
+        for (long long mi = 0; mi * MG_TILE_M < counts[e]; ++mi, ++row_tile) {
+            std::fill(u.begin(), u.end(), (uint64_t)0);
+            const long long valid = std::min<long long>(MG_TILE_M, counts[e] - mi * MG_TILE_M);
+            for (long long r = 0; r < valid; ++r) {
+                const uint64_t s = (uint64_t)(start + mi * MG_TILE_M + r);
+                const uint64_t p = gs_weight(wbase + s);
+                const uint64_t at = base + (uint64_t)mg_row_id(base, s, (uint32_t)tokens) * (uint64_t)k;
+                uint64_t* const row = &u[(size_t)(r / (MG_TILE_M / 2) * k)];
+                for (long long kk = 0; kk < k; ++kk)
+                    row[kk] += p * (uint64_t)(int64_t)gs_element(at + (uint64_t)kk, GS_MOD_A);
+            }
+            for (long long w = 0; w < nt * MS_WAVES_PER_WG; ++w) {
+                const long long tj = w / MS_WAVES_PER_WG, wr = w >> 1 & 1, wc = w & 1;
+                const uint64_t* const ur = &u[(size_t)(wr * k)];
+                const uint64_t* const vr = &v[(size_t)((tj * 2 + wc) * k)];
+                uint64_t dot = 0;
+                for (long long kk = 0; kk < k; ++kk) dot += ur[kk] * vr[kk];
+                out[row_tile * nt * MS_WAVES_PER_WG + w] = (uint64_t)reps * dot;
+            }
+        }
+    }
+}
+
+// What the host entry points that take counts check. bk: the dtype's, or the
+// smaller of the two where no dtype is at hand.
+static int mg_host_args(const char* fn, long long tokens, long long slots, int experts,
+                        long long n, long long k, const int* counts, int reps, long long bk) {
+    if (!mg_shape_ok(tokens, slots, experts, n, k, reps, bk) || counts == nullptr)
+        return arg_error("%s: need " MG_SHAPE_WORDS " and counts (%p)", fn,
+                         MG_SHAPE_ARGS(tokens, slots, experts, n, k, reps, bk),
+                         (const void*)counts);
+    const int bad = mg_bad_count(counts, experts, slots);
+    if (bad >= 0)
+        return arg_error("%s: need " MG_COUNT_WORDS " (expert %d has %d, slots %lld)", fn, bad,
+                         counts[bad], slots);
+    return NA_OK;
+}
+
+static int mg_dtype_ok(const char* fn, int dtype) {
+    if (dtype != MS_BF16 && dtype != MS_FP8)
+        return arg_error("%s: need dtype 0 (bf16) or 1 (fp8) (got %d)", fn, dtype);
+    return NA_OK;
+}
+
+// Pure host code: all 4 * bound checksums, n_out exactly that.
+extern "C" int na_moe_gemm_expected(unsigned long long seed, long long tokens, long long slots,
+                                    int experts, long long n_cols, long long k, const int* counts,
+                                    int reps, uint64_t* checksums, long long n_out) {
+    const int rc = mg_host_args("na_moe_gemm_expected", tokens, slots, experts, n_cols, k, counts,
+                                reps, NA_GEMM_BK_BF16);
+    if (rc != NA_OK) return rc;
+    if (checksums == nullptr || n_out != MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols))
+        return arg_error("na_moe_gemm_expected: need room for exactly 4 checksums per workgroup "
+                         "(checksums %p, n_out %lld, want %lld)",
+                         (void*)checksums, n_out,
+                         MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols));
+    mg_expected(seed * MS_G, tokens, slots, experts, n_cols, k, counts, reps, checksums);
+    return NA_OK;
+}
+
+// Writes X (tokens x k) and W (experts x n_cols x k) of `seed` in `dtype`, the
+// hashed row_ids[slots] and the prefix sums of `counts` as offsets[experts + 1]
+// into caller-owned device memory.
+extern "C" int na_moe_gemm_fill(int dev, int dtype, void* x, void* w, void* row_ids, void* offsets,
+                                long long tokens, long long slots, int experts, long long n_cols,
+                                long long k, const int* counts, unsigned long long seed) {
+    int rc = mg_dtype_ok("na_moe_gemm_fill", dtype);
+    if (rc != NA_OK) return rc;
+    rc = mg_host_args("na_moe_gemm_fill", tokens, slots, experts, n_cols, k, counts, 1,
+                      gs_bk(dtype));
+    if (rc != NA_OK) return rc;
+    if (x == nullptr || w == nullptr || row_ids == nullptr || offsets == nullptr ||
+        (((uintptr_t)x | (uintptr_t)w) & 15) != 0 ||
+        (((uintptr_t)row_ids | (uintptr_t)offsets) & 3) != 0)
+        return arg_error("na_moe_gemm_fill: need 16-byte aligned x and w (got %p, %p) and 4-byte "
+                         "aligned row_ids and offsets (%p, %p)",
+                         x, w, row_ids, offsets);
+    HIP_CHECK(hipSetDevice(dev));
+    std::vector<int> sums((size_t)experts + 1, 0);
+    for (int e = 0; e < experts; ++e) sums[(size_t)e + 1] = sums[(size_t)e] + counts[e];
+    HIP_CHECK(hipMemcpy(offsets, sums.data(), sums.size() * sizeof(int), hipMemcpyHostToDevice));
+    const uint64_t per_vec = 16 / (dtype == MS_FP8 ? 1 : 2);
+    const uint64_t x_vecs = (uint64_t)(tokens * k) / per_vec;
+    const uint64_t w_vecs = (uint64_t)experts * (uint64_t)(n_cols * k) / per_vec;
+    const uint64_t threads = x_vecs + w_vecs + (uint64_t)slots;
+    mg_launch_fill(dtype, (unsigned)((threads + MS_BLOCK - 1) / MS_BLOCK), static_cast<mt_vec*>(x),
+                   static_cast<mt_vec*>(w), static_cast<int*>(row_ids), x_vecs, w_vecs,
+                   (uint32_t)slots, (uint32_t)tokens, seed * MS_G);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+// One HIP-event timed expert GEMM on caller-owned device tensors: the bound of
+// (slots / 128 + experts) * n_cols / 256 workgroups, each of which finds its
+// tile in `offsets` or reports idle. c, when not null, receives the rows of the
+// slots below offsets[experts]; out the 4 records per workgroup, whose
+// checksums match na_moe_gemm_expected when the tensors are na_moe_gemm_fill's
+// of the same seed and shape. The host never reads offsets or row_ids, and no
+// content of them takes a read outside the four arrays. Argument errors are
+// detected before any HIP call.
+extern "C" int na_moe_gemm_run(int dev, int dtype, const void* x, const void* w,
+                               const void* row_ids, const void* offsets, void* c,
+                               long long tokens, long long slots, int experts, long long n_cols,
+                               long long k, int reps, unsigned long long seed, na_mfma_record* out,
+                               long long n_out, double* ms) {
+    int rc = mg_dtype_ok("na_moe_gemm_run", dtype);
+    if (rc != NA_OK) return rc;
+    if (!mg_shape_ok(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype)))
+        return arg_error("na_moe_gemm_run: need " MG_SHAPE_WORDS,
+                         MG_SHAPE_ARGS(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype)));
+    if (x == nullptr || w == nullptr || row_ids == nullptr || offsets == nullptr ||
+        (((uintptr_t)x | (uintptr_t)w) & 15) != 0 ||
+        (((uintptr_t)row_ids | (uintptr_t)offsets | (uintptr_t)c) & 3) != 0)
+        return arg_error("na_moe_gemm_run: need 16-byte aligned x and w (got %p, %p), 4-byte "
+                         "aligned row_ids and offsets (%p, %p) and c null or 4-byte aligned (%p)",
+                         x, w, row_ids, offsets, c);
+    const long long bound = mg_bound(slots, experts, n_cols);
+    if (out == nullptr || n_out != MS_WAVES_PER_WG * bound)
+        return arg_error("na_moe_gemm_run: need room for exactly 4 records per workgroup (out %p, "
+                         "n_out %lld, want %lld)",
+                         (void*)out, n_out, MS_WAVES_PER_WG * bound);
+    size_t lds_bytes = 0;
+    rc = sweep_lds_bytes(dev, &lds_bytes);
+    if (rc != NA_OK) return rc;
+    if (lds_bytes < MG_LDS_BYTES)
+        return arg_error("na_moe_gemm_run: the device's %zu-byte per-workgroup LDS allocation is "
+                         "under the %d bytes of the two stages",
+                         lds_bytes, MG_LDS_BYTES);
+    const uint64_t wbase = seed * MS_G + (uint64_t)tokens * (uint64_t)k +
+                           (uint64_t)experts * (uint64_t)n_cols * (uint64_t)k;
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        mg_launch_sweep(dtype, (unsigned)bound, records, static_cast<const mt_vec*>(x),
+                        static_cast<const mt_vec*>(w), static_cast<const int*>(row_ids),
+                        static_cast<const int*>(offsets), static_cast<float*>(c),
+                        (uint32_t)tokens, (uint32_t)slots, (uint32_t)experts,
+                        (uint32_t)(n_cols / MG_TILE_N), (uint32_t)(k / gs_bk(dtype)),
+                        (uint32_t)reps, wbase);
+    });
+}
+
+// Pure host code. Record i < 4 * tiles is wave 4 * tile + 2 * wr + wc of a real
+// tile; the records behind them must be idle: checksum 0 and their own index
+// (ms_tally's rules with a want of 0, so exactly the surplus records are idle:
+// an idle record in a tile's place fails as does work in a surplus one).
+// Returns NA_ERR_VERIFY on any bad record, with a message that names the first
+// by unit, expert, row tile and sub-tile; *res is filled either way.
+extern "C" int na_moe_gemm_verify(const na_mfma_record* recs, long long n, long long tokens,
+                                  long long slots, int experts, long long n_cols, long long k,
+                                  const int* counts, int reps, unsigned long long seed,
+                                  na_mfma_sweep_result* res) {
+    const int rc = mg_host_args("na_moe_gemm_verify", tokens, slots, experts, n_cols, k, counts,
+                                reps, NA_GEMM_BK_BF16);
+    if (rc != NA_OK) return rc;
+    if (recs == nullptr || n != MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols) ||
+        res == nullptr)
+        return arg_error("na_moe_gemm_verify: need exactly 4 records per workgroup (recs %p, n "
+                         "%lld, want %lld) and a result pointer",
+                         (const void*)recs, n, MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols));
+    std::vector<uint64_t> want((size_t)n);
+    mg_expected(seed * MS_G, tokens, slots, experts, n_cols, k, counts, reps, want.data());
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const long long w = (long long)res->first_bad_wave, nt = n_cols / MG_TILE_N;
+    long long row_tile = w / MS_WAVES_PER_WG / nt;
+    char what[112];
+    std::snprintf(what, sizeof(what), "a surplus workgroup that must report idle");
+    for (int e = 0; e < experts; ++e) {
+        const long long mine = (counts[e] + MG_TILE_M - 1) / MG_TILE_M;
+        if (row_tile < mine) {
+            std::snprintf(what, sizeof(what), "expert %d row tile %lld column tile %lld sub-tile "
+                          "%lld,%lld", e, row_tile, w / MS_WAVES_PER_WG % nt, w >> 1 & 1, w & 1);
+            break;
+        }
+        row_tile -= mine;
+    }
+    return na_error(NA_ERR_VERIFY,
+                    "moe gemm sweep: %llu of %llu records wrong on %llu CU(s), first record %lld "
+                    "(%s) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, what, u[0], u[1], u[2], u[3], u[4]);
+}
+
+// The whole sweep's counts: expert e draws h = mix64(seed G - 2^40 - e); h % 8
+// = 0 is an empty expert, 1 an expert of one slot, anything else avg / 2 + (h >>
+// 8) % (3 avg / 2 + 1) slots with avg = slots / experts, cut where the slots
+// run out. What is left over are dropped tokens.
+static std::vector<int> mg_default_counts(uint64_t base, long long slots, int experts) {
+    std::vector<int> counts((size_t)experts);
+    const long long avg = slots / experts;
+    long long left = slots;
+    for (int e = 0; e < experts; ++e) {
+        const uint64_t h = mt_mix64(base - ((uint64_t)1 << 40) - (uint64_t)e);
+        const long long draw = h % 8 == 0   ? 0
+                               : h % 8 == 1 ? 1
+                                            : avg / 2 + (long long)((h >> 8) % (uint64_t)(3 * avg / 2 + 1));
+        counts[(size_t)e] = (int)std::min(draw, left);
+        left -= counts[(size_t)e];
+    }
+    return counts;
+}
+
+// Whole sweep on tensors the agent allocates and fills itself: one untimed
+// warm-up launch, the timed launch, the verify. 0 = default for tokens (8192),
+// slots (4 tokens), experts (32), n_cols (2048), k (1024) and reps; the counts
+// are mg_default_counts'. *tflops counts 2 * n_cols * k * reps FLOP per valid
+// slot over the event time. Operands over half of the free device memory, or
+// that cannot be allocated, are NA_ERR_ARG.
+extern "C" int na_moe_gemm_sweep(int dev, int dtype, long long tokens, long long slots,
+                                 int experts, long long n_cols, long long k, int reps,
+                                 unsigned long long seed, na_mfma_sweep_result* res,
+                                 double* tflops) {
+    if ((dtype != MS_BF16 && dtype != MS_FP8) || res == nullptr || tokens < 0 || slots < 0 ||
+        experts < 0 || n_cols < 0 || k < 0 || reps < 0)
+        return arg_error("na_moe_gemm_sweep: need dtype 0 (bf16) or 1 (fp8) (got %d), tokens, "
+                         "slots, experts, n_cols, k and reps >= 0 (got %lld, %lld, %d, %lld, %lld, "
+                         "%d) and a result pointer",
+                         dtype, tokens, slots, experts, n_cols, k, reps);
+    if (tokens == 0) tokens = NA_MOE_DEFAULT_TOKENS;
+    if (slots == 0) slots = std::min<long long>(NA_MOE_DEFAULT_TOPK * tokens, NA_MOE_MAX_ROWS);
+    if (experts == 0) experts = NA_MOE_DEFAULT_EXPERTS;
+    if (n_cols == 0) n_cols = NA_MOE_DEFAULT_N;
+    if (k == 0) k = NA_MOE_DEFAULT_K;
+    if (reps == 0) reps = mg_default_reps[dtype];
+    if (!mg_shape_ok(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype)))
+        return arg_error("na_moe_gemm_sweep: need " MG_SHAPE_WORDS,
+                         MG_SHAPE_ARGS(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype)));
+    const std::vector<int> counts = mg_default_counts(seed * MS_G, slots, experts);
+    double valid = 0.0;
+    for (int count : counts) valid += count;
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t esize = dtype == MS_FP8 ? 1 : 2;
+    const size_t sizes[4] = {(size_t)(tokens * k) * esize, (size_t)experts * (size_t)(n_cols * k) * esize,
+                             (size_t)slots * sizeof(int), ((size_t)experts + 1) * sizeof(int)};
+    dev_buf<unsigned char> bufs[4];
+    int rc = gs_alloc("na_moe_gemm_sweep", bufs, sizes, 4, tokens, (long long)experts * n_cols, k);
+    if (rc != NA_OK) return rc;
+    rc = na_moe_gemm_fill(dev, dtype, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, tokens, slots,
+                          experts, n_cols, k, counts.data(), seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs((size_t)(MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols)));
+    double ms = 0.0;
+    rc = sweep_twice([&] {
+        return na_moe_gemm_run(dev, dtype, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, nullptr,
+                               tokens, slots, experts, n_cols, k, reps, seed, recs.data(),
+                               (long long)recs.size(), &ms);
+    });
+    if (rc != NA_OK) return rc;
+    if (tflops) *tflops = 2.0 * valid * (double)n_cols * (double)k * reps / (ms * 1e9);
+    return na_moe_gemm_verify(recs.data(), (long long)recs.size(), tokens, slots, experts, n_cols,
+                              k, counts.data(), reps, seed, res);
+}

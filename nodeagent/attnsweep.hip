@@ -13,9 +13,13 @@
 // The decode attention sweep's kernels (decodesweep.h) are built here too, for
 // the same reason: its merges and rescales are claimed exact.
 
+// The MoE grouped GEMM sweep's kernels (moegemmsweep.h) too: new code whose
+// verdict is bit-exact goes here, not beside the vector-unit sweep.
+
 #define AS_KERNELS
 #include "attnsweep.h"
 #include "decodesweep.h"
+#include "moegemmsweep.h"
 
 void as_launch_fill(unsigned grid, mt_vec* q, mt_vec* k, mt_vec* v, mt_u64 q_vecs, mt_u64 kv_vecs,
                     mt_u64 n_k, as_layout at) {
@@ -49,4 +53,21 @@ void ds_launch_combine(na_mfma_record* records, const float* workspace, float* o
                        uint32_t heads, uint32_t kv_heads, uint32_t splits, float c, mt_u64 wbase) {
     decode_combine_kernel<<<dim3(batch * kv_heads), dim3(MS_BLOCK)>>>(
         records, workspace, o, batch, heads, kv_heads, splits, c, wbase);
+}
+
+void mg_launch_fill(int dtype, unsigned grid, mt_vec* x, mt_vec* w, int* row_ids, mt_u64 x_vecs,
+                    mt_u64 w_vecs, uint32_t slots, uint32_t tokens, mt_u64 base) {
+    (dtype == MS_FP8 ? moe_fill_kernel<MS_FP8> : moe_fill_kernel<MS_BF16>)<<<dim3(grid),
+                                                                            dim3(MS_BLOCK)>>>(
+        x, w, row_ids, x_vecs, w_vecs, slots, tokens, base);
+}
+
+void mg_launch_sweep(int dtype, unsigned grid, na_mfma_record* records, const mt_vec* x,
+                     const mt_vec* w, const int* row_ids, const int* offsets, float* c,
+                     uint32_t tokens, uint32_t slots, uint32_t experts, uint32_t nt,
+                     uint32_t ksteps, uint32_t reps, mt_u64 wbase) {
+    (dtype == MS_FP8 ? moe_gemm_kernel<MS_FP8> : moe_gemm_kernel<MS_BF16>)<<<dim3(grid),
+                                                                            dim3(MS_BLOCK),
+                                                                            MG_LDS_BYTES>>>(
+        records, x, w, row_ids, offsets, c, tokens, slots, experts, nt, ksteps, reps, wbase);
 }

@@ -65,6 +65,10 @@
 #define NA_DECODE_MAX_PAGES (1 << 16)  // and pages in a row of the block table,
 #define NA_DECODE_MAX_SPLITS 64  // at most this many workgroups share a (sequence, KV head),
 #define NA_DECODE_EXACT (1 << 24)  // and 256 * reps * the longest length stays under this
+#define NA_MOE_TILE_M 128        // slots in a tile of the MoE grouped GEMM sweep: a tile has one expert;
+#define NA_MOE_TILE_N 256        // its N is a multiple of this (K and reps as the GEMM sweep's),
+#define NA_MOE_MAX_EXPERTS 256   // with at most this many experts
+#define NA_MOE_MAX_ROWS (1 << 22)  // and tokens and slots
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -86,7 +90,10 @@
 // (decodesweep.h) leaves it for each wave of each split of each (sequence, KV
 // head), `wave` being 4 * ((b * kv_heads + hk) * splits + split) + wave, and
 // after those one per (sequence, KV head) over the merged state, `wave` being 4
-// * batch * kv_heads * splits + b * kv_heads + hk.
+// * batch * kv_heads * splits + b * kv_heads + hk. The MoE grouped GEMM sweep
+// (moegemmsweep.h) leaves it for each wave of each tile, `wave` being 4 * tile
+// + 2 * wr + wc, and with checksum 0 for each wave of the workgroups beyond the
+// last tile.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -422,6 +429,39 @@ int na_decode_sweep_verify(const na_mfma_record* recs, long long n, int batch, i
                            unsigned long long seed, na_mfma_sweep_result* res);
 int na_decode_sweep(int dev, int batch, int heads, int kv_heads, int max_pages, int splits,
                     int reps, unsigned long long seed, na_mfma_sweep_result* res, double* gbps);
+
+// chip-wide MoE grouped GEMM sweep, and the expert GEMM it runs as an operation
+// on caller-owned tensors: C[s] = reps * X[row_ids[s]] * W[e]^T for the slots s
+// of expert e, offsets[e] <= s < offsets[e+1]. dtype 0 = bf16, 1 = fp8; x is
+// tokens x k and w experts x n_cols x k, K-contiguous in that dtype, row_ids
+// int32[slots] and offsets int32[experts + 1] in device memory, c null or slots
+// x n_cols floats (rows from offsets[experts] on are never written); n_cols a
+// multiple of 256, k and reps as the GEMM sweep's; `counts` is the host's copy
+// of the slots per expert, their sum at most `slots`. Tiles of 128 slots x 256
+// columns are found on the device, so a launch has na_moe_gemm_tiles' `bound`
+// workgroups, (slots / 128 + experts) * n_cols / 256, and leaves 4 * bound
+// records: 4 * tile + 2 * wr + wc for the wave of the 64 x 128 sub-tile (wr,
+// wc) of a tile, tiles numbered by expert, row tile, column tile, and idle
+// records behind them. Operands and checksums in moegemmsweep.h; results are
+// the matrix-core sweep's. 0 = the default for na_moe_gemm_sweep's shape and
+// reps, its counts are hashed from the seed.
+int na_moe_gemm_tiles(long long slots, int experts, long long n_cols, long long* bound);
+int na_moe_gemm_fill(int dev, int dtype, void* x, void* w, void* row_ids, void* offsets,
+                     long long tokens, long long slots, int experts, long long n_cols, long long k,
+                     const int* counts, unsigned long long seed);
+int na_moe_gemm_expected(unsigned long long seed, long long tokens, long long slots, int experts,
+                         long long n_cols, long long k, const int* counts, int reps,
+                         uint64_t* checksums, long long n_out);
+int na_moe_gemm_run(int dev, int dtype, const void* x, const void* w, const void* row_ids,
+                    const void* offsets, void* c, long long tokens, long long slots, int experts,
+                    long long n_cols, long long k, int reps, unsigned long long seed,
+                    na_mfma_record* out, long long n_out, double* ms);
+int na_moe_gemm_verify(const na_mfma_record* recs, long long n, long long tokens, long long slots,
+                       int experts, long long n_cols, long long k, const int* counts, int reps,
+                       unsigned long long seed, na_mfma_sweep_result* res);
+int na_moe_gemm_sweep(int dev, int dtype, long long tokens, long long slots, int experts,
+                      long long n_cols, long long k, int reps, unsigned long long seed,
+                      na_mfma_sweep_result* res, double* tflops);
 
 #ifdef __cplusplus
 }
