@@ -8,7 +8,8 @@ there is no eager/python fallback for the hardware checks.
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
 [--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]
-[--mxquant-sweep] [--attn-sweep] [--decode-sweep] [--moe-gemm-sweep]``
+[--mxquant-sweep] [--attn-sweep] [--decode-sweep] [--moe-gemm-sweep]
+[--moe-route-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
 from __future__ import annotations
@@ -285,6 +286,27 @@ MOE_MAX_EXPERTS = 256
 # random data. The device-to-device spread of this kernel has not been
 # measured; 0.70 is borrowed from the MFMA floor. 0 disables the floor.
 MIN_MOE_GEMM_SWEEP_TFLOPS = 360.5
+
+# Chip-wide MoE routing sweep (nodeagent/moeroutesweep.h): the two ends of a
+# mixture-of-experts layer around the expert GEMM: the router (weights and
+# top-k by DPP row operations), the stable sort of (token, choice) pairs into
+# expert-major slots (LDS atomic masks, a prefix sum on the device, a scatter),
+# and the weighted combine of the GEMM's rows back into token order. Also three
+# operations on caller-owned tensors (``moe_route_run``, ``moe_sort_run``,
+# ``moe_combine_run``). The default seed is "MI355XMR".
+DEFAULT_MOE_ROUTE_SWEEP_SEED = 0x4D493335_35584D52
+# nodeagent/nodeagent.h: NA_MOE_MAX_TOPK, NA_MOE_ROUTE_BLOCK, NA_MOE_COMBINE_WAVE_TOKENS
+MOE_MAX_TOPK = 8
+MOE_ROUTE_BLOCK = 256  # tokens of a route or scatter workgroup: 4 records
+MOE_COMBINE_WAVE_TOKENS = 8  # tokens of a combine wave: 1 record
+# Floors of the default sweep (65536 tokens top-4 on 128 experts, rows of 1024
+# floats): 0.70 x the medians of five processes on MI355X, 1166.8 Mtoken/s
+# through route + sort and 5348.0 GB/s of the combine
+# (profiles/moe_route_sweep_mi355x.txt), the rule of the floors above. The
+# device-to-device spread of these kernels has not been measured; 0.70 is
+# borrowed from the MFMA floor. 0 disables a floor.
+MIN_MOE_ROUTE_SWEEP_MTOKS = 816.8
+MIN_MOE_COMBINE_SWEEP_GBPS = 3743.6
 
 # check()'s boolean self-tests in order: (method, GPUReport field, problem label)
 _SELFTESTS = (
@@ -614,6 +636,45 @@ class MoeGemmSweepResult:
         return (
             f"{self.sweep.describe()}; first record {w} ({what} sub-tile {w >> 1 & 1},{w & 1}) on "
             f"{mfma_unit_name(self.sweep.bad_simds[0])}"
+        )
+
+
+def moe_route_records(tokens: int) -> tuple:
+    """The records the route, the scatter and the combine leave for ``tokens``:
+    4 per 256 tokens each of the first two, one per wave of 8 tokens (4 per
+    workgroup) of the third."""
+    blocks = -(-tokens // MOE_ROUTE_BLOCK)
+    return 4 * blocks, 4 * blocks, 4 * -(-tokens // (4 * MOE_COMBINE_WAVE_TOKENS))
+
+
+@dataclass
+class MoeRouteSweepResult:
+    """Outcome of a MoE routing sweep verify: the matrix-core sweep's result
+    over the records of the route, the scatter and the combine, one kernel
+    behind the other, and the rates of the timed window (0 when only a verify
+    was done)."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    tokens: int = 0
+    mtoks: float = 0.0  # million tokens a second through route + sort
+    gbps: float = 0.0  # the combine's bytes of Y read plus out written
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong record by kernel, tokens
+        and unit."""
+        w, (route, scatter, _) = self.sweep.first_bad_wave, moe_route_records(self.tokens)
+        if w < route + scatter:
+            kernel, first, per = ("route", "scatter")[w >= route], w % route * 64, 64
+        else:
+            kernel, per = "combine", MOE_COMBINE_WAVE_TOKENS
+            first = (w - route - scatter) * per
+        return (
+            f"{self.sweep.describe()}; first record {w} ({kernel}, tokens {first}.."
+            f"{min(first + per, self.tokens) - 1}) on {mfma_unit_name(self.sweep.bad_simds[0])}"
         )
 
 
@@ -1020,6 +1081,22 @@ _ABI = {
     "na_moe_gemm_sweep": (
         _int, (_int, _int, _i64, _i64, _int, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC),
                _double_p)),
+    "na_moe_route_fill": (_int, (_int, _void_p, _void_p, _i64, _int, _int, _i64, _u64)),
+    "na_moe_route_expected": (_int, (_u64, _i64, _int, _int, _i64, _int, _u64_p, _i64)),
+    "na_moe_route_run": (
+        _int, (_int, _void_p, _void_p, _void_p, _void_p, _i64, _int, _int, ctypes.c_float, _int,
+               _u64, _P(MfmaRecord), _i64, _double_p)),
+    "na_moe_sort_run": (
+        _int, (_int, _void_p, _void_p, _void_p, _void_p, _i64, _int, _int, _u64, _P(MfmaRecord),
+               _i64, _double_p)),
+    "na_moe_combine_run": (
+        _int, (_int, _void_p, _void_p, _void_p, _void_p, _void_p, _void_p, _i64, _int, _i64, _u64,
+               _P(MfmaRecord), _i64, _double_p)),
+    "na_moe_route_verify": (
+        _int, (_P(MfmaRecord), _i64, _i64, _int, _int, _i64, _int, _u64, _P(_MfmaSweepResultC))),
+    "na_moe_route_sweep": (
+        _int, (_int, _i64, _int, _int, _i64, _int, _u64, _P(_MfmaSweepResultC), _double_p,
+               _double_p)),
 }
 
 
@@ -1116,6 +1193,13 @@ class GPUReport:
     moe_gemm_sweep_units_seen: int = 0
     moe_gemm_sweep_bad_waves: int = 0  # tile records and idle records
     moe_gemm_sweep_skipped: str = ""  # reason, when requested but not run
+    # chip-wide MoE routing sweep (opt-in)
+    moe_route_sweep_mtoks: float = 0.0  # million tokens a second, route + sort
+    moe_combine_sweep_gbps: float = 0.0  # Y read plus out written
+    moe_route_sweep_clock_mhz: float = 0.0  # informational, no floor
+    moe_route_sweep_units_seen: int = 0
+    moe_route_sweep_bad_waves: int = 0  # route, scatter and combine records
+    moe_route_sweep_skipped: str = ""  # reason, when requested but not run
     sdma_bw_gbs: float = 0.0
     healthy: bool = False
     problems: list = field(default_factory=list)
@@ -2462,6 +2546,132 @@ class NodeAgent:
             # the library's message names the expert: only it knows the sweep's counts
             g.problems.append(f"MoE GEMM sweep: {res.describe()}; {self._err()}")
 
+    # -- chip-wide MoE routing sweep -------------------------------------------------
+
+    def moe_route_fill(self, dev: int, logits: int, y: int, tokens: int, experts: int, top_k: int,
+                       n: int, seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> None:
+        """Write the sweep's hashed bf16 ``logits`` (``tokens`` x ``experts``)
+        and, when ``y`` is not 0, the float32 rows ``y`` (``tokens * top_k`` x
+        ``n``) into device memory the caller owns (device pointers as
+        integers)."""
+        rc = self.lib.na_moe_route_fill(dev, logits, y or None, tokens, experts, top_k, n, seed)
+        self._check(rc, f"moe_route_fill({dev})")
+
+    def moe_route_expected(self, tokens: int, experts: int, top_k: int, n: int, renorm: int = 0,
+                           seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> list:
+        """Reference checksums of every record of the route, the scatter and
+        the combine on ``moe_route_fill``'s tensors with ``scale_log2`` 1, one
+        kernel behind the other (``moe_route_records``). Host integer
+        arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * sum(moe_route_records(tokens)))()
+        rc = self.lib.na_moe_route_expected(seed, tokens, experts, top_k, n, renorm, out, len(out))
+        self._check(rc, "moe_route_expected")
+        return list(out)
+
+    def moe_route_run(self, dev: int, logits: int, topk_ids: int, topk_p: int, denom: int,
+                      tokens: int, experts: int, top_k: int, scale_log2: float = 1.0,
+                      renorm: int = 0, seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> tuple:
+        """One launch of the router, all device memory: bf16 ``logits``
+        (``tokens`` x ``experts``) in; int32 ``topk_ids`` and float32 ``topk_p``
+        (``tokens`` x ``top_k``; ``exp2(scale_log2 * (logit - max))``,
+        unnormalised) and float32 ``denom[tokens]`` out: the sum of the weights
+        over all experts, or over the chosen ones with ``renorm`` 1. Returns
+        ``(records, ms)``."""
+        recs = (MfmaRecord * moe_route_records(tokens)[0])()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_moe_route_run(dev, logits, topk_ids, topk_p, denom, tokens, experts, top_k,
+                                       scale_log2, renorm, seed, recs, len(recs), ctypes.byref(ms))
+        self._check(rc, f"moe_route_run({dev})")
+        return recs, ms.value
+
+    def moe_sort_run(self, dev: int, topk_ids: int, offsets: int, row_ids: int, slot_of: int,
+                     tokens: int, experts: int, top_k: int,
+                     seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> tuple:
+        """The stable sort of the (token, choice) pairs of int32 ``topk_ids``
+        into expert-major slots, three launches, all device memory: int32
+        ``offsets[experts + 1]`` and ``row_ids[tokens * top_k]`` out, which is
+        what ``moe_gemm_run`` reads, and ``slot_of`` (``tokens`` x ``top_k``),
+        the inverse. Returns ``(records, ms)`` of the scatter."""
+        recs = (MfmaRecord * moe_route_records(tokens)[1])()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_moe_sort_run(dev, topk_ids, offsets, row_ids, slot_of, tokens, experts,
+                                      top_k, seed, recs, len(recs), ctypes.byref(ms))
+        self._check(rc, f"moe_sort_run({dev})")
+        return recs, ms.value
+
+    def moe_combine_run(self, dev: int, y: int, slot_of: int, row_ids: int, topk_p: int,
+                        denom: int, out: int, tokens: int, top_k: int, n: int,
+                        seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> tuple:
+        """``out[t] = (sum_j topk_p[t][j] * y[slot_of[t][j]]) * (1 / denom[t])``,
+        all device memory: float32 ``y`` (``tokens * top_k`` x ``n``, the expert
+        GEMM's C) in, float32 ``out`` (``tokens`` x ``n``) out. Returns
+        ``(records, ms)``."""
+        recs = (MfmaRecord * moe_route_records(tokens)[2])()
+        ms = ctypes.c_double(0)
+        rc = self.lib.na_moe_combine_run(dev, y, slot_of, row_ids, topk_p, denom, out, tokens, top_k,
+                                         n, seed, recs, len(recs), ctypes.byref(ms))
+        self._check(rc, f"moe_combine_run({dev})")
+        return recs, ms.value
+
+    def moe_route_verify(self, recs, tokens: int, experts: int, top_k: int, n: int,
+                         renorm: int = 0, seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> tuple:
+        """Compare the records of the three kernels, one behind the other,
+        against the host reference of ``moe_route_fill``'s tensors. Returns
+        ``(rc, MoeRouteSweepResult)``; rc is ``NA_ERR_VERIFY`` on any bad
+        record, and ``na_last_error`` then names the first by kernel, tokens
+        and unit."""
+        res = _MfmaSweepResultC()
+        rc = self.lib.na_moe_route_verify(recs, len(recs), tokens, experts, top_k, n, renorm, seed,
+                                          ctypes.byref(res))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            return rc, MoeRouteSweepResult()
+        return rc, MoeRouteSweepResult(MfmaSweepResult._from_c("bf16", res), tokens)
+
+    def moe_route_sweep(self, dev: int, tokens: int = 0, experts: int = 0, top_k: int = 0,
+                        n: int = 0, reps: int = 0,
+                        seed: int = DEFAULT_MOE_ROUTE_SWEEP_SEED) -> MoeRouteSweepResult:
+        """Allocate and fill the tensors, run route, sort and combine once
+        untimed, then ``reps`` passes of route + sort and ``reps`` of the
+        combine in one timed window, and verify every record bit-exactly. 0
+        selects the default: 65536 tokens, 128 experts, top-4, rows of 1024
+        floats and the ``reps`` of a 16-19 ms window. Wrong records come back in
+        the result (``.ok`` False), not as an exception; tensors that do not
+        fit in half of the free device memory raise ``GemmSweepNoRoom``."""
+        res, mtoks, gbps = _MfmaSweepResultC(), ctypes.c_double(0), ctypes.c_double(0)
+        rc = self.lib.na_moe_route_sweep(dev, tokens, experts, top_k, n, reps, seed,
+                                         ctypes.byref(res), ctypes.byref(mtoks), ctypes.byref(gbps))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = GemmSweepNoRoom if "do not fit" in err else NodeAgentError
+            raise cls(f"moe_route_sweep({dev}): {err}")
+        return MoeRouteSweepResult(MfmaSweepResult._from_c("bf16", res), tokens or 65536,
+                                   mtoks.value, gbps.value)
+
+    def _run_moe_route_sweep(self, g: GPUReport) -> None:
+        try:
+            res = self.moe_route_sweep(g.index)
+        except GemmSweepNoRoom as e:
+            # a busy GPU must not get its node replaced for lack of free memory
+            g.moe_route_sweep_skipped = str(e)
+            return
+        g.moe_route_sweep_mtoks = round(res.mtoks, 1)
+        g.moe_combine_sweep_gbps = round(res.gbps, 1)
+        g.moe_route_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+        g.moe_route_sweep_units_seen = res.sweep.units_seen
+        g.moe_route_sweep_bad_waves = res.sweep.bad_waves
+        if res.mtoks < MIN_MOE_ROUTE_SWEEP_MTOKS:
+            g.problems.append(
+                f"MoE routing sweep {g.moe_route_sweep_mtoks} Mtoken/s below floor "
+                f"{MIN_MOE_ROUTE_SWEEP_MTOKS}"
+            )
+        if res.gbps < MIN_MOE_COMBINE_SWEEP_GBPS:
+            g.problems.append(
+                f"MoE combine sweep {g.moe_combine_sweep_gbps} GB/s below floor "
+                f"{MIN_MOE_COMBINE_SWEEP_GBPS}"
+            )
+        if not res.ok:
+            g.problems.append(f"MoE routing sweep: {res.describe()}")
+
     def p2p_matrix(self, n: int) -> list:
         buf = (ctypes.c_int * (n * n))()
         self._check(self.lib.na_p2p_matrix(n, buf), "p2p_matrix")
@@ -2482,7 +2692,7 @@ class NodeAgent:
               load_sweep: bool = False, gemm_sweep: bool = False,
               mxgemm_sweep: bool = False, mxquant_sweep: bool = False,
               attn_sweep: bool = False, decode_sweep: bool = False,
-              moe_gemm_sweep: bool = False) -> NodeReport:
+              moe_gemm_sweep: bool = False, moe_route_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -2583,6 +2793,15 @@ class NodeAgent:
         and unit, as is a rate over the valid rows under
         ``MIN_MOE_GEMM_SWEEP_TFLOPS``; operands that do not fit land in
         ``moe_gemm_sweep_skipped``. False (default) makes no new library
+        call.
+
+        ``moe_route_sweep`` additionally runs the chip-wide MoE routing sweep
+        on every GPU: router, stable sort into expert-major slots and weighted
+        combine on hashed operands, every wave of the three kernels verified
+        exactly. A wrong record is a problem that names its kernel, tokens and
+        unit, as is a rate under ``MIN_MOE_ROUTE_SWEEP_MTOKS`` or
+        ``MIN_MOE_COMBINE_SWEEP_GBPS``; tensors that do not fit land in
+        ``moe_route_sweep_skipped``. False (default) makes no new library
         call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
@@ -2643,6 +2862,8 @@ class NodeAgent:
                     self._run_decode_sweep(g)
                 if moe_gemm_sweep:
                     self._run_moe_gemm_sweep(g)
+                if moe_route_sweep:
+                    self._run_moe_route_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -2857,6 +3078,17 @@ def main(argv=None) -> int:
         "tile and sub-tile; reports the rate over the valid rows",
     )
     ap.add_argument(
+        "--moe-route-sweep",
+        action="store_true",
+        help="also run the chip-wide MoE routing sweep on every GPU: the router (weights and top-k "
+        "by DPP row operations, ties to the lower expert), the stable sort of (token, choice) pairs "
+        "into expert-major slots (LDS atomic masks, a prefix sum on the device, a scatter) and the "
+        "weighted combine of the expert rows back into token order, on hashed operands; every "
+        "wave's checksum of the three kernels is recomputed on the host in integers and a wrong "
+        "one attributed to its XCC/SE/SH/CU/SIMD, kernel and tokens; reports tokens per second "
+        "through route + sort and the combine's bytes per second",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -2882,6 +3114,7 @@ def main(argv=None) -> int:
             attn_sweep=args.attn_sweep,
             decode_sweep=args.decode_sweep,
             moe_gemm_sweep=args.moe_gemm_sweep,
+            moe_route_sweep=args.moe_route_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

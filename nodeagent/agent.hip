@@ -50,6 +50,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -4341,4 +4342,350 @@ extern "C" int na_moe_gemm_sweep(int dev, int dtype, long long tokens, long long
     if (tflops) *tflops = 2.0 * valid * (double)n_cols * (double)k * reps / (ms * 1e9);
     return na_moe_gemm_verify(recs.data(), (long long)recs.size(), tokens, slots, experts, n_cols,
                               k, counts.data(), reps, seed, res);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide MoE routing sweep (specification and kernels in moeroutesweep.h,
+// the kernels compiled in attnsweep.hip)
+// ---------------------------------------------------------------------------
+//
+// The two ends of a mixture-of-experts layer around the expert GEMM above: the
+// router (weights and top-k), the stable sort of (token, choice) pairs into
+// expert-major slots, which leaves the row_ids and offsets na_moe_gemm_run
+// reads, and the weighted combine of the GEMM's rows back into token order. As
+// a sweep every wave's checksum is recomputed by the host in integers; as
+// operations (na_moe_route_run, na_moe_sort_run, na_moe_combine_run) they take
+// any tensors.
+
+#include "moeroutesweep.h"
+
+// The whole sweep's shape: 65536 tokens routed top-4 to 128 experts, rows of N
+// = 1024 floats: 1 GiB of Y, 256 MiB of out.
+#define NA_MOE_ROUTE_DEFAULT_TOKENS 65536
+#define NA_MOE_ROUTE_DEFAULT_EXPERTS 128
+#define NA_MOE_ROUTE_DEFAULT_TOPK 4
+#define NA_MOE_ROUTE_DEFAULT_N 1024
+// Passes of route + sort, then as many of the combine, in one timed window.
+// Chosen on the MI355X for a window of 16-19 ms: 0.056 ms a pass of route +
+// sort and 0.252 ms of the combine measured
+// (profiles/moe_route_sweep_mi355x.txt).
+#define NA_MOE_ROUTE_DEFAULT_REPS 56
+#define NA_MOE_ROUTE_MAX_N (1 << 16)
+
+static bool mr_shape_ok(long long tokens, int experts, int top_k, long long n) {
+    return tokens >= 1 && top_k >= 1 && top_k <= NA_MOE_MAX_TOPK && top_k <= experts &&
+           experts <= NA_MOE_MAX_EXPERTS && tokens * top_k <= NA_MOE_MAX_ROWS && n >= 4 &&
+           n <= NA_MOE_ROUTE_MAX_N && n % 4 == 0;
+}
+
+#define MR_SHAPE_WORDS                                                                        \
+    "top_k in 1..%d (got %d), experts in top_k..%d (got %d), tokens >= 1 with tokens * top_k " \
+    "<= %d (got %lld), n_cols a multiple of 4 in 4..%d (got %lld)"
+#define MR_SHAPE_ARGS(tokens, experts, top_k, n)                                             \
+    NA_MOE_MAX_TOPK, top_k, NA_MOE_MAX_EXPERTS, experts, NA_MOE_MAX_ROWS, (long long)(tokens), \
+        NA_MOE_ROUTE_MAX_N, (long long)(n)
+
+static mr_layout mr_at(unsigned long long seed, long long tokens, int experts, int top_k) {
+    return mr_layout{seed * MS_G, (uint32_t)tokens, (uint32_t)experts, (uint32_t)top_k,
+                     (uint32_t)(tokens * top_k)};
+}
+
+// Records of the route and of the scatter (each), and of the combine.
+static long long mr_route_records(long long tokens) { return MS_WAVES_PER_WG * (long long)mr_blocks(tokens); }
+static long long mr_combine_records(long long tokens) {
+    return MS_WAVES_PER_WG * (long long)mr_combine_blocks(tokens);
+}
+static long long mr_records(long long tokens) {
+    return 2 * mr_route_records(tokens) + mr_combine_records(tokens);
+}
+
+// All checksums of the hashed problem in integers: the route's, the scatter's,
+// the combine's. O(tokens * experts * top_k + slots + n).
+static void mr_expected(const mr_layout& at, long long n, int renorm, uint64_t* out) {
+    const long long tokens = at.tokens, slots = at.slots;
+    const int experts = (int)at.experts, top_k = (int)at.top_k;
+    const long long nr = mr_route_records(tokens);
+    std::fill(out, out + mr_records(tokens), (uint64_t)0);
+    // route: ids by (larger logit, lower index), 256 p = 2^(8 + logit - max)
+    std::vector<int> ids((size_t)slots), p256((size_t)slots), logit((size_t)experts);
+    std::vector<int> counts((size_t)experts + 1, 0);
+    for (long long t = 0; t < tokens; ++t) {
+        int top = INT_MIN;
+        for (int e = 0; e < experts; ++e) top = std::max(top, logit[(size_t)e] = at.logit((uint64_t)t, (uint64_t)e));
+        long long all = 0, chosen = 0;
+        for (int e = 0; e < experts; ++e) all += 1LL << (8 + logit[(size_t)e] - top);
+        uint64_t& sum = out[t / 64];
+        for (int j = 0; j < top_k; ++j) {
+            int best = 0;
+            for (int e = 1; e < experts; ++e)
+                if (logit[(size_t)e] > logit[(size_t)best]) best = e;
+            const uint64_t s = (uint64_t)(t * top_k + j);
+            ids[s] = best;
+            p256[s] = 1 << (8 + logit[(size_t)best] - top);
+            chosen += p256[s];
+            counts[(size_t)best]++;
+            logit[(size_t)best] = INT_MIN;
+            sum += at.w_id(s) * (uint64_t)best + at.w_p(s) * (uint64_t)p256[s];
+        }
+        sum += at.w_denom((uint64_t)t) * (uint64_t)(renorm ? chosen : all);
+    }
+    // sort: tokens ascend, so walking them in order hands out stable slots
+    std::vector<int> next((size_t)experts, 0), slot_of((size_t)slots);
+    for (int e = 1; e < experts; ++e) next[(size_t)e] = next[(size_t)e - 1] + counts[(size_t)e - 1];
+    for (long long s = 0; s < slots; ++s) {
+        slot_of[(size_t)s] = next[(size_t)ids[(size_t)s]]++;
+        out[nr + s / top_k / 64] += at.w_slot((uint64_t)s) * (uint64_t)(slot_of[(size_t)s] + 1);
+    }
+    // combine: 256 * sum_t[n] = A_t g_n + B_t h_n
+    uint64_t qg = 0, qh = 0;
+    for (long long c = 0; c < n; ++c) {
+        const uint64_t x = at.y_col((uint64_t)c, (uint64_t)n), q = at.w_col((uint64_t)c);
+        qg += q * (uint64_t)(int64_t)mr_factor_a(x);
+        qh += q * (uint64_t)(int64_t)mr_factor_b(x);
+    }
+    for (long long t = 0; t < tokens; ++t) {
+        int64_t a = 0, b = 0;
+        uint64_t& sum = out[2 * nr + t / MR_WAVE_TOKENS];
+        for (int j = 0; j < top_k; ++j) {
+            const uint64_t s = (uint64_t)(t * top_k + j);
+            const uint64_t x = at.y_row((uint64_t)slot_of[s]);
+            a += (int64_t)p256[s] * mr_factor_a(x);
+            b += (int64_t)p256[s] * mr_factor_b(x);
+            sum += at.w_row(s) * (uint64_t)(t + 1);  // row_ids[slot_of[t][j]] is t
+        }
+        sum += at.w_token((uint64_t)t) * (qg * (uint64_t)a + qh * (uint64_t)b);
+    }
+}
+
+// Pure host code: all 2 * 4 * blocks + 4 * combine blocks checksums.
+extern "C" int na_moe_route_expected(unsigned long long seed, long long tokens, int experts,
+                                     int top_k, long long n_cols, int renorm, uint64_t* checksums,
+                                     long long n_out) {
+    if (!mr_shape_ok(tokens, experts, top_k, n_cols) || (renorm != 0 && renorm != 1))
+        return arg_error("na_moe_route_expected: need " MR_SHAPE_WORDS " and renorm 0 or 1 (got %d)",
+                         MR_SHAPE_ARGS(tokens, experts, top_k, n_cols), renorm);
+    if (checksums == nullptr || n_out != mr_records(tokens))
+        return arg_error("na_moe_route_expected: need room for exactly the records of the three "
+                         "kernels (checksums %p, n_out %lld, want %lld)",
+                         (void*)checksums, n_out, mr_records(tokens));
+    mr_expected(mr_at(seed, tokens, experts, top_k), n_cols, renorm, checksums);
+    return NA_OK;
+}
+
+// Writes the hashed bf16 logits (tokens x experts) and, when y is not null, Y
+// (tokens * top_k x n_cols floats) of `seed` into caller-owned device memory.
+extern "C" int na_moe_route_fill(int dev, void* logits, void* y, long long tokens, int experts,
+                                 int top_k, long long n_cols, unsigned long long seed) {
+    if (!mr_shape_ok(tokens, experts, top_k, n_cols))
+        return arg_error("na_moe_route_fill: need " MR_SHAPE_WORDS,
+                         MR_SHAPE_ARGS(tokens, experts, top_k, n_cols));
+    if (logits == nullptr || (((uintptr_t)logits | (uintptr_t)y) & 15) != 0)
+        return arg_error("na_moe_route_fill: need 16-byte aligned logits (got %p) and y null or "
+                         "16-byte aligned (%p)", logits, y);
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t threads = (uint64_t)tokens * (uint64_t)experts +
+                             (y ? (uint64_t)(tokens * top_k) * (uint64_t)(n_cols / 4) : 0);
+    mr_launch_fill((unsigned)((threads + MS_BLOCK - 1) / MS_BLOCK),
+                   static_cast<unsigned short*>(logits), static_cast<float*>(y),
+                   mr_at(seed, tokens, experts, top_k), (uint32_t)n_cols);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return NA_OK;
+}
+
+static int mr_records_ok(const char* fn, const na_mfma_record* out, long long n_out, long long want) {
+    if (out == nullptr || n_out != want)
+        return arg_error("%s: need room for exactly one record per wave (out %p, n_out %lld, want "
+                         "%lld)", fn, (const void*)out, n_out, want);
+    return NA_OK;
+}
+
+// One HIP-event timed route on caller-owned device tensors: logits bf16 tokens
+// x experts in, topk_ids int32 and topk_p float tokens x top_k and denom
+// float[tokens] out; 4 records per 256 tokens. Argument errors are detected
+// before any HIP call.
+extern "C" int na_moe_route_run(int dev, const void* logits, void* topk_ids, void* topk_p,
+                                void* denom, long long tokens, int experts, int top_k,
+                                float scale_log2, int renorm, unsigned long long seed,
+                                na_mfma_record* out, long long n_out, double* ms) {
+    if (!mr_shape_ok(tokens, experts, top_k, 4) || (renorm != 0 && renorm != 1))
+        return arg_error("na_moe_route_run: need " MR_SHAPE_WORDS " and renorm 0 or 1 (got %d)",
+                         MR_SHAPE_ARGS(tokens, experts, top_k, 4), renorm);
+    if (logits == nullptr || topk_ids == nullptr || topk_p == nullptr || denom == nullptr ||
+        ((uintptr_t)logits & 15) != 0 ||
+        (((uintptr_t)topk_ids | (uintptr_t)topk_p | (uintptr_t)denom) & 3) != 0)
+        return arg_error("na_moe_route_run: need 16-byte aligned logits (got %p) and 4-byte aligned "
+                         "topk_ids, topk_p and denom (%p, %p, %p)", logits, topk_ids, topk_p, denom);
+    const int rc = mr_records_ok("na_moe_route_run", out, n_out, mr_route_records(tokens));
+    if (rc != NA_OK) return rc;
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        mr_launch_route(records, static_cast<const unsigned short*>(logits),
+                        static_cast<int*>(topk_ids), static_cast<float*>(topk_p),
+                        static_cast<float*>(denom), mr_at(seed, tokens, experts, top_k), scale_log2,
+                        (uint32_t)renorm);
+    });
+}
+
+// One HIP-event timed sort (count, scan, scatter: three launches) on
+// caller-owned device tensors: topk_ids in, offsets int32[experts + 1], row_ids
+// int32[tokens * top_k] and slot_of int32 tokens x top_k out: what
+// na_moe_gemm_run reads. 4 records of the scatter per 256 tokens, numbered
+// behind the route's. The counts per block are in a workspace of the call.
+extern "C" int na_moe_sort_run(int dev, const void* topk_ids, void* offsets, void* row_ids,
+                               void* slot_of, long long tokens, int experts, int top_k,
+                               unsigned long long seed, na_mfma_record* out, long long n_out,
+                               double* ms) {
+    if (!mr_shape_ok(tokens, experts, top_k, 4))
+        return arg_error("na_moe_sort_run: need " MR_SHAPE_WORDS,
+                         MR_SHAPE_ARGS(tokens, experts, top_k, 4));
+    if (topk_ids == nullptr || offsets == nullptr || row_ids == nullptr || slot_of == nullptr ||
+        (((uintptr_t)topk_ids | (uintptr_t)offsets | (uintptr_t)row_ids | (uintptr_t)slot_of) & 3) != 0)
+        return arg_error("na_moe_sort_run: need 4-byte aligned topk_ids, offsets, row_ids and "
+                         "slot_of (got %p, %p, %p, %p)", topk_ids, offsets, row_ids, slot_of);
+    const int rc = mr_records_ok("na_moe_sort_run", out, n_out, mr_route_records(tokens));
+    if (rc != NA_OK) return rc;
+    HIP_CHECK(hipSetDevice(dev));
+    dev_buf<int> counts;
+    HIP_CHECK(counts.alloc((size_t)mr_blocks(tokens) * (size_t)experts));
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        mr_launch_sort(records, static_cast<const int*>(topk_ids), counts.p,
+                       static_cast<int*>(offsets), static_cast<int*>(row_ids),
+                       static_cast<int*>(slot_of), mr_at(seed, tokens, experts, top_k),
+                       (uint32_t)mr_route_records(tokens));
+    });
+}
+
+// One HIP-event timed combine on caller-owned device tensors: y float tokens *
+// top_k x n_cols (the expert GEMM's C), slot_of, row_ids, topk_p, denom in,
+// out_rows float tokens x n_cols out. One record per wave of 8 tokens, numbered
+// behind the scatter's.
+extern "C" int na_moe_combine_run(int dev, const void* y, const void* slot_of, const void* row_ids,
+                                  const void* topk_p, const void* denom, void* out_rows,
+                                  long long tokens, int top_k, long long n_cols,
+                                  unsigned long long seed, na_mfma_record* out, long long n_out,
+                                  double* ms) {
+    if (!mr_shape_ok(tokens, NA_MOE_MAX_EXPERTS, top_k, n_cols))
+        return arg_error("na_moe_combine_run: need " MR_SHAPE_WORDS,
+                         MR_SHAPE_ARGS(tokens, NA_MOE_MAX_EXPERTS, top_k, n_cols));
+    if (y == nullptr || slot_of == nullptr || row_ids == nullptr || topk_p == nullptr ||
+        denom == nullptr || out_rows == nullptr || (((uintptr_t)y | (uintptr_t)out_rows) & 15) != 0 ||
+        (((uintptr_t)slot_of | (uintptr_t)row_ids | (uintptr_t)topk_p | (uintptr_t)denom) & 3) != 0)
+        return arg_error("na_moe_combine_run: need 16-byte aligned y and out_rows (got %p, %p) and "
+                         "4-byte aligned slot_of, row_ids, topk_p and denom (%p, %p, %p, %p)", y,
+                         out_rows, slot_of, row_ids, topk_p, denom);
+    const int rc = mr_records_ok("na_moe_combine_run", out, n_out, mr_combine_records(tokens));
+    if (rc != NA_OK) return rc;
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        mr_launch_combine(records, static_cast<const float*>(y), static_cast<const int*>(slot_of),
+                          static_cast<const int*>(row_ids), static_cast<const float*>(topk_p),
+                          static_cast<const float*>(denom), static_cast<float*>(out_rows),
+                          mr_at(seed, tokens, 1, top_k), (uint32_t)n_cols,
+                          (uint32_t)(2 * mr_route_records(tokens)));
+    });
+}
+
+// Pure host code over the records of the three kernels, one behind the other:
+// route, scatter, combine. Returns NA_ERR_VERIFY on any bad record, with a
+// message that names the first by kernel, tokens and unit; *res is filled
+// either way.
+extern "C" int na_moe_route_verify(const na_mfma_record* recs, long long n, long long tokens,
+                                   int experts, int top_k, long long n_cols, int renorm,
+                                   unsigned long long seed, na_mfma_sweep_result* res) {
+    if (!mr_shape_ok(tokens, experts, top_k, n_cols) || (renorm != 0 && renorm != 1))
+        return arg_error("na_moe_route_verify: need " MR_SHAPE_WORDS " and renorm 0 or 1 (got %d)",
+                         MR_SHAPE_ARGS(tokens, experts, top_k, n_cols), renorm);
+    if (recs == nullptr || n != mr_records(tokens) || res == nullptr)
+        return arg_error("na_moe_route_verify: need exactly the records of the three kernels (recs "
+                         "%p, n %lld, want %lld) and a result pointer",
+                         (const void*)recs, n, mr_records(tokens));
+    std::vector<uint64_t> want((size_t)n);
+    mr_expected(mr_at(seed, tokens, experts, top_k), n_cols, renorm, want.data());
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const long long w = (long long)res->first_bad_wave, nr = mr_route_records(tokens);
+    const char* const kernel = w < nr ? "route" : w < 2 * nr ? "scatter" : "combine";
+    const long long per = w < 2 * nr ? 64 : MR_WAVE_TOKENS;
+    const long long first = (w < 2 * nr ? w % nr : w - 2 * nr) * per;
+    return na_error(NA_ERR_VERIFY,
+                    "moe route sweep: %llu of %llu records wrong on %llu CU(s), first record %lld "
+                    "(%s, tokens %lld..%lld) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, kernel, first,
+                    std::min(first + per, tokens) - 1, u[0], u[1], u[2], u[3], u[4]);
+}
+
+// Whole sweep on tensors the agent allocates and fills itself: one untimed pass
+// of route, sort and combine, then `reps` passes of route + sort and `reps` of
+// the combine back to back in one timed window with an event between the two,
+// then the verify of the last pass's records. 0 = default for tokens (65536),
+// experts (128), top_k (4), n_cols (1024) and reps; scale_log2 = 1, renorm = 0.
+// *mtoks: million tokens per second through route + sort; *gbps: bytes of Y
+// read plus out written per second of the combine. Tensors over half of the
+// free device memory, or that cannot be allocated, are NA_ERR_ARG.
+extern "C" int na_moe_route_sweep(int dev, long long tokens, int experts, int top_k,
+                                  long long n_cols, int reps, unsigned long long seed,
+                                  na_mfma_sweep_result* res, double* mtoks, double* gbps) {
+    if (res == nullptr || tokens < 0 || experts < 0 || top_k < 0 || n_cols < 0 || reps < 0)
+        return arg_error("na_moe_route_sweep: need tokens, experts, top_k, n_cols and reps >= 0 (got "
+                         "%lld, %d, %d, %lld, %d) and a result pointer",
+                         tokens, experts, top_k, n_cols, reps);
+    if (tokens == 0) tokens = NA_MOE_ROUTE_DEFAULT_TOKENS;
+    if (experts == 0) experts = NA_MOE_ROUTE_DEFAULT_EXPERTS;
+    if (top_k == 0) top_k = NA_MOE_ROUTE_DEFAULT_TOPK;
+    if (n_cols == 0) n_cols = NA_MOE_ROUTE_DEFAULT_N;
+    if (reps == 0) reps = NA_MOE_ROUTE_DEFAULT_REPS;
+    if (!mr_shape_ok(tokens, experts, top_k, n_cols))
+        return arg_error("na_moe_route_sweep: need " MR_SHAPE_WORDS,
+                         MR_SHAPE_ARGS(tokens, experts, top_k, n_cols));
+    HIP_CHECK(hipSetDevice(dev));
+    const mr_layout at = mr_at(seed, tokens, experts, top_k);
+    const size_t slots = at.slots, nr = (size_t)mr_route_records(tokens);
+    const size_t n_recs = (size_t)mr_records(tokens);
+    enum { LOGITS, IDS, P, DENOM, OFFSETS, ROWS, SLOT_OF, COUNTS, Y, OUT, RECS, BUFS };
+    const size_t sizes[BUFS] = {(size_t)tokens * experts * 2, slots * 4, slots * 4,
+                                (size_t)tokens * 4, ((size_t)experts + 1) * 4, slots * 4, slots * 4,
+                                (size_t)mr_blocks(tokens) * experts * 4, slots * n_cols * 4,
+                                (size_t)tokens * n_cols * 4, n_recs * sizeof(na_mfma_record)};
+    dev_buf<unsigned char> bufs[BUFS];
+    int rc = gs_alloc("na_moe_route_sweep", bufs, sizes, BUFS, (long long)slots, tokens, n_cols);
+    if (rc != NA_OK) return rc;
+    rc = na_moe_route_fill(dev, bufs[LOGITS].p, bufs[Y].p, tokens, experts, top_k, n_cols, seed);
+    if (rc != NA_OK) return rc;
+    na_mfma_record* const recs_d = reinterpret_cast<na_mfma_record*>(bufs[RECS].p);
+    HIP_CHECK(hipMemset(recs_d, 0xFF, sizes[RECS]));
+    auto as_int = [&](int i) { return reinterpret_cast<int*>(bufs[i].p); };
+    auto as_float = [&](int i) { return reinterpret_cast<float*>(bufs[i].p); };
+    auto route_and_sort = [&] {
+        mr_launch_route(recs_d, reinterpret_cast<const unsigned short*>(bufs[LOGITS].p), as_int(IDS),
+                        as_float(P), as_float(DENOM), at, 1.f, 0);
+        mr_launch_sort(recs_d + nr, as_int(IDS), as_int(COUNTS), as_int(OFFSETS), as_int(ROWS),
+                       as_int(SLOT_OF), at, (uint32_t)nr);
+    };
+    auto combine = [&] {
+        mr_launch_combine(recs_d + 2 * nr, as_float(Y), as_int(SLOT_OF), as_int(ROWS), as_float(P),
+                          as_float(DENOM), as_float(OUT), at, (uint32_t)n_cols, (uint32_t)(2 * nr));
+    };
+    route_and_sort();  // the untimed pass
+    combine();
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    dev_events<3> ev;
+    for (hipEvent_t& e : ev.e) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(ev.e[0]));
+    for (int i = 0; i < reps; ++i) route_and_sort();
+    HIP_CHECK(hipEventRecord(ev.e[1]));
+    for (int i = 0; i < reps; ++i) combine();
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[2]));
+    HIP_CHECK(hipEventSynchronize(ev.e[2]));
+    float ms_route = 0.f, ms_combine = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms_route, ev.e[0], ev.e[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms_combine, ev.e[1], ev.e[2]));
+    std::vector<na_mfma_record> recs(n_recs);
+    HIP_CHECK(hipMemcpy(recs.data(), recs_d, sizes[RECS], hipMemcpyDeviceToHost));
+    if (mtoks) *mtoks = (double)tokens * reps / ((double)ms_route * 1e3);
+    if (gbps) *gbps = (double)(sizes[Y] + sizes[OUT]) * reps / ((double)ms_combine * 1e6);
+    return na_moe_route_verify(recs.data(), (long long)n_recs, tokens, experts, top_k, n_cols, 0,
+                               seed, res);
 }

@@ -16,10 +16,14 @@
 // The MoE grouped GEMM sweep's kernels (moegemmsweep.h) too: new code whose
 // verdict is bit-exact goes here, not beside the vector-unit sweep.
 
+// The MoE routing sweep's kernels (moeroutesweep.h) as well: its weights and
+// the combine's FMA chain are claimed exact.
+
 #define AS_KERNELS
 #include "attnsweep.h"
 #include "decodesweep.h"
 #include "moegemmsweep.h"
+#include "moeroutesweep.h"
 
 void as_launch_fill(unsigned grid, mt_vec* q, mt_vec* k, mt_vec* v, mt_u64 q_vecs, mt_u64 kv_vecs,
                     mt_u64 n_k, as_layout at) {
@@ -70,4 +74,33 @@ void mg_launch_sweep(int dtype, unsigned grid, na_mfma_record* records, const mt
                                                                             dim3(MS_BLOCK),
                                                                             MG_LDS_BYTES>>>(
         records, x, w, row_ids, offsets, c, tokens, slots, experts, nt, ksteps, reps, wbase);
+}
+
+void mr_launch_fill(unsigned grid, unsigned short* logits, float* y, mr_layout at, uint32_t n_cols) {
+    moe_route_fill_kernel<<<dim3(grid), dim3(MS_BLOCK)>>>(logits, y, at, n_cols);
+}
+
+void mr_launch_route(na_mfma_record* records, const unsigned short* logits, int* topk_ids,
+                     float* topk_p, float* denom, mr_layout at, float scale_log2, uint32_t renorm) {
+    (at.experts > 128 ? moe_route_kernel<2> : moe_route_kernel<1>)<<<dim3(mr_blocks(at.tokens)),
+                                                                    dim3(MS_BLOCK)>>>(
+        records, logits, topk_ids, topk_p, denom, at, scale_log2, renorm);
+}
+
+// The sort's three launches: count, scan, scatter. block_counts: mr_blocks x
+// experts ints.
+void mr_launch_sort(na_mfma_record* records, const int* topk_ids, int* block_counts, int* offsets,
+                    int* row_ids, int* slot_of, mr_layout at, uint32_t wave0) {
+    const uint32_t blocks = mr_blocks(at.tokens);
+    moe_route_count_kernel<<<dim3(blocks), dim3(MS_BLOCK)>>>(topk_ids, block_counts, at);
+    moe_route_scan_kernel<<<dim3(1), dim3(MS_BLOCK)>>>(block_counts, offsets, at, blocks);
+    moe_route_scatter_kernel<<<dim3(blocks), dim3(MS_BLOCK)>>>(records, topk_ids, block_counts,
+                                                               offsets, row_ids, slot_of, at, wave0);
+}
+
+void mr_launch_combine(na_mfma_record* records, const float* y, const int* slot_of,
+                       const int* row_ids, const float* topk_p, const float* denom, float* out,
+                       mr_layout at, uint32_t n_cols, uint32_t wave0) {
+    moe_combine_kernel<<<dim3(mr_combine_blocks(at.tokens)), dim3(MS_BLOCK)>>>(
+        records, y, slot_of, row_ids, topk_p, denom, out, at, n_cols, wave0);
 }

@@ -69,6 +69,9 @@
 #define NA_MOE_TILE_N 256        // its N is a multiple of this (K and reps as the GEMM sweep's),
 #define NA_MOE_MAX_EXPERTS 256   // with at most this many experts
 #define NA_MOE_MAX_ROWS (1 << 22)  // and tokens and slots
+#define NA_MOE_MAX_TOPK 8        // choices of a token in the MoE routing sweep,
+#define NA_MOE_ROUTE_BLOCK 256   // tokens of a workgroup of its route and sort (4 records),
+#define NA_MOE_COMBINE_WAVE_TOKENS 8  // and of a wave of its combine (1 record)
 
 // ---------------------------------------------------------------------------
 // Records: what the sweep kernels write, one per wave or workgroup
@@ -93,7 +96,9 @@
 // * batch * kv_heads * splits + b * kv_heads + hk. The MoE grouped GEMM sweep
 // (moegemmsweep.h) leaves it for each wave of each tile, `wave` being 4 * tile
 // + 2 * wr + wc, and with checksum 0 for each wave of the workgroups beyond the
-// last tile.
+// last tile. The MoE routing sweep (moeroutesweep.h) leaves it for each wave of
+// its route, scatter and combine kernels, numbered one kernel behind the other
+// as its prototypes below say.
 typedef struct {
     uint64_t checksum, cycles, realtime;
     uint32_t wave, xcc, se, sh, cu, simd;
@@ -462,6 +467,44 @@ int na_moe_gemm_verify(const na_mfma_record* recs, long long n, long long tokens
 int na_moe_gemm_sweep(int dev, int dtype, long long tokens, long long slots, int experts,
                       long long n_cols, long long k, int reps, unsigned long long seed,
                       na_mfma_sweep_result* res, double* tflops);
+
+// chip-wide MoE routing sweep, and the three operations it runs on caller-owned
+// tensors around the expert GEMM above (specification, operands and checksums
+// in moeroutesweep.h). Route: logits bf16 tokens x experts -> topk_ids int32 and
+// topk_p float (unnormalised exp2(scale_log2 (logit - max))) tokens x top_k,
+// denom float[tokens] (the sum of p over all experts, or over the chosen ones
+// with renorm 1). Sort: topk_ids -> offsets int32[experts + 1], row_ids
+// int32[tokens * top_k] (what na_moe_gemm_run reads) and slot_of int32 tokens x
+// top_k. Combine: out_rows[t] = (sum_j topk_p[t][j] * y[slot_of[t][j]]) * (1 /
+// denom[t]), y float tokens * top_k x n_cols, n_cols a multiple of 4. top_k in
+// 1..8, top_k <= experts <= 256, tokens * top_k <= NA_MOE_MAX_ROWS. Records,
+// with B = ceil(tokens / 256): the route's are 0 .. 4B-1, wave w of block b at 4b
+// + w over tokens 256b + 64w ..; the scatter's 4B .. 8B-1 over the same tokens;
+// the combine's from 8B, one per wave of 8 tokens, 4 * ceil(tokens / 32) of
+// them. na_moe_route_run, na_moe_sort_run and na_moe_combine_run each take room
+// for their own kernel's records; `expected` and `verify` take all, one behind
+// the other. Results are the matrix-core sweep's. 0 = the default for
+// na_moe_route_sweep's shape and reps.
+int na_moe_route_fill(int dev, void* logits, void* y, long long tokens, int experts, int top_k,
+                      long long n_cols, unsigned long long seed);
+int na_moe_route_expected(unsigned long long seed, long long tokens, int experts, int top_k,
+                          long long n_cols, int renorm, uint64_t* checksums, long long n_out);
+int na_moe_route_run(int dev, const void* logits, void* topk_ids, void* topk_p, void* denom,
+                     long long tokens, int experts, int top_k, float scale_log2, int renorm,
+                     unsigned long long seed, na_mfma_record* out, long long n_out, double* ms);
+int na_moe_sort_run(int dev, const void* topk_ids, void* offsets, void* row_ids, void* slot_of,
+                    long long tokens, int experts, int top_k, unsigned long long seed,
+                    na_mfma_record* out, long long n_out, double* ms);
+int na_moe_combine_run(int dev, const void* y, const void* slot_of, const void* row_ids,
+                       const void* topk_p, const void* denom, void* out_rows, long long tokens,
+                       int top_k, long long n_cols, unsigned long long seed, na_mfma_record* out,
+                       long long n_out, double* ms);
+int na_moe_route_verify(const na_mfma_record* recs, long long n, long long tokens, int experts,
+                        int top_k, long long n_cols, int renorm, unsigned long long seed,
+                        na_mfma_sweep_result* res);
+int na_moe_route_sweep(int dev, long long tokens, int experts, int top_k, long long n_cols,
+                       int reps, unsigned long long seed, na_mfma_sweep_result* res, double* mtoks,
+                       double* gbps);
 
 #ifdef __cplusplus
 }
