@@ -8,7 +8,7 @@ there is no eager/python fallback for the hardware checks.
 CLI: ``python -m gpu_provisioner_amd.nodeagent [--json] [--expect-gpus N]
 [--memtest-bytes N] [--mfma-sweep] [--mx-checks] [--mx-sweep] [--lds-sweep]
 [--cache-sweep] [--valu-sweep] [--load-sweep] [--gemm-sweep] [--mxgemm-sweep]
-[--mxquant-sweep] [--attn-sweep] [--decode-sweep] [--moe-gemm-sweep]
+[--mxquant-sweep] [--attn-sweep] [--decode-sweep] [--moe-gemm-sweep] [--moe-skinny-sweep]
 [--moe-route-sweep]``
 Exit 0 = healthy, 1 = unhealthy/degraded, 2 = agent error.
 """
@@ -286,6 +286,29 @@ MOE_MAX_EXPERTS = 256
 # random data. The device-to-device spread of this kernel has not been
 # measured; 0.70 is borrowed from the MFMA floor. 0 disables the floor.
 MIN_MOE_GEMM_SWEEP_TFLOPS = 360.5
+
+# Chip-wide decode-size MoE expert GEMM sweep (nodeagent/moeskinnysweep.h): the
+# same operation on the same tensors (``moe_gemm_fill`` fills for both) at decode
+# counts, 1-16 slots per expert: tiles of 16 slots x 256 columns, the expert's
+# weights streamed from HBM straight into the matrix cores, the figure bytes per
+# second. Also an operation on caller-owned tensors (``moe_skinny_run``). The
+# default seed is "MI355XMS"; ``4 * moe_skinny_tiles(...)`` records.
+DEFAULT_MOE_SKINNY_SWEEP_SEED = 0x4D493335_35584D53
+# nodeagent/nodeagent.h: NA_MOE_SKINNY_TILE_M
+MOE_SKINNY_TILE_M = 16
+# The default sweep's shape (nodeagent/agent.hip: NA_MOE_SKINNY_DEFAULT_*): a
+# decode step of 160 tokens top-8 on 128 experts, 1 GiB of bf16 weights.
+DEFAULT_MOE_SKINNY_SWEEP_TOKENS = 160
+DEFAULT_MOE_SKINNY_SWEEP_TOPK = 8
+DEFAULT_MOE_SKINNY_SWEEP_EXPERTS = 128
+DEFAULT_MOE_SKINNY_SWEEP_N = 2048
+DEFAULT_MOE_SKINNY_SWEEP_K = 2048
+# Floor of the default sweep in GB/s (weights of the experts that have a slot,
+# gathered rows and result rows per second), bf16: 0.70 x the 5199.1 GB/s median
+# of five processes on MI355X (profiles/moe_skinny_sweep_mi355x.txt), the rule of
+# the floors above. The device-to-device spread of this kernel has not been
+# measured; 0.70 is borrowed from the MFMA floor. 0 disables the floor.
+MIN_MOE_SKINNY_SWEEP_GBPS = 3639.4
 
 # Chip-wide MoE routing sweep (nodeagent/moeroutesweep.h): the two ends of a
 # mixture-of-experts layer around the expert GEMM: the router (weights and
@@ -635,6 +658,43 @@ class MoeGemmSweepResult:
                 what = "a surplus workgroup that must report idle"
         return (
             f"{self.sweep.describe()}; first record {w} ({what} sub-tile {w >> 1 & 1},{w & 1}) on "
+            f"{mfma_unit_name(self.sweep.bad_simds[0])}"
+        )
+
+
+@dataclass
+class MoeSkinnySweepResult:
+    """Outcome of a decode-size MoE expert GEMM sweep verify: the matrix-core
+    sweep's result over the 4 records of every workgroup of the launch bound
+    (tiles first, idle records behind them), and the bytes per second of the
+    timed launches (0 when only a verify was done). ``counts`` are the slots
+    per expert where the caller knows them."""
+
+    sweep: MfmaSweepResult = field(default_factory=MfmaSweepResult)
+    n: int = 0
+    counts: tuple = ()
+    gbps: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.sweep.ok
+
+    def describe(self) -> str:
+        """The failing units, then the first wrong record by expert, row tile,
+        column tile and wave (by tile, without the counts) and unit."""
+        w, nt = self.sweep.first_bad_wave, max(self.n // MOE_TILE_N, 1)
+        what, tile = f"tile {w // 4}", w // 4
+        for e, count in enumerate(self.counts):
+            mine = -(-count // MOE_SKINNY_TILE_M)
+            if tile < mine * nt:
+                what = f"expert {e} row tile {tile % mine} column tile {tile // mine}"
+                break
+            tile -= mine * nt
+        else:
+            if self.counts:
+                what = "a surplus workgroup that must report idle"
+        return (
+            f"{self.sweep.describe()}; first record {w} ({what} wave {w % 4}) on "
             f"{mfma_unit_name(self.sweep.bad_simds[0])}"
         )
 
@@ -1081,6 +1141,18 @@ _ABI = {
     "na_moe_gemm_sweep": (
         _int, (_int, _int, _i64, _i64, _int, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC),
                _double_p)),
+    "na_moe_skinny_tiles": (_int, (_i64, _int, _i64, _i64_p)),
+    "na_moe_skinny_expected": (
+        _int, (_u64, _i64, _i64, _int, _i64, _i64, _int_p, _int, _u64_p, _i64)),
+    "na_moe_skinny_run": (
+        _int, (_int, _int, _void_p, _void_p, _void_p, _void_p, _void_p, _i64, _i64, _int, _i64,
+               _i64, _int, _u64, _P(MfmaRecord), _i64, _double_p)),
+    "na_moe_skinny_verify": (
+        _int, (_P(MfmaRecord), _i64, _i64, _i64, _int, _i64, _i64, _int_p, _int, _u64,
+               _P(_MfmaSweepResultC))),
+    "na_moe_skinny_sweep": (
+        _int, (_int, _int, _i64, _i64, _int, _i64, _i64, _int, _u64, _P(_MfmaSweepResultC),
+               _double_p)),
     "na_moe_route_fill": (_int, (_int, _void_p, _void_p, _i64, _int, _int, _i64, _u64)),
     "na_moe_route_expected": (_int, (_u64, _i64, _int, _int, _i64, _int, _u64_p, _i64)),
     "na_moe_route_run": (
@@ -1193,6 +1265,11 @@ class GPUReport:
     moe_gemm_sweep_units_seen: int = 0
     moe_gemm_sweep_bad_waves: int = 0  # tile records and idle records
     moe_gemm_sweep_skipped: str = ""  # reason, when requested but not run
+    moe_skinny_sweep_gbps: float = 0.0  # weights of active experts, X rows and C rows
+    moe_skinny_sweep_clock_mhz: float = 0.0  # informational, no floor
+    moe_skinny_sweep_units_seen: int = 0
+    moe_skinny_sweep_bad_waves: int = 0  # tile records and idle records
+    moe_skinny_sweep_skipped: str = ""  # reason, when requested but not run
     # chip-wide MoE routing sweep (opt-in)
     moe_route_sweep_mtoks: float = 0.0  # million tokens a second, route + sort
     moe_combine_sweep_gbps: float = 0.0  # Y read plus out written
@@ -2546,6 +2623,102 @@ class NodeAgent:
             # the library's message names the expert: only it knows the sweep's counts
             g.problems.append(f"MoE GEMM sweep: {res.describe()}; {self._err()}")
 
+    # -- chip-wide decode-size MoE expert GEMM sweep -----------------------------------
+
+    def moe_skinny_tiles(self, slots: int, experts: int, n: int) -> int:
+        """The workgroups a launch takes, ``(slots // 16 + experts) * n // 256``:
+        an upper bound of the tiles, which only the device knows. A launch
+        leaves 4 records for each. Needs no GPU."""
+        out = ctypes.c_longlong(0)
+        self._check(self.lib.na_moe_skinny_tiles(slots, experts, n, ctypes.byref(out)),
+                    "moe_skinny_tiles")
+        return out.value
+
+    def moe_skinny_expected(self, tokens: int, slots: int, n: int, k: int, counts, reps: int = 1,
+                            seed: int = DEFAULT_MOE_SKINNY_SWEEP_SEED) -> list:
+        """Reference checksums of every record of a launch on ``moe_gemm_fill``'s
+        tensors of ``seed``: ``4 * tile + wave`` over the wave's 64 columns and
+        the tile's valid rows, tiles by expert, column tile and row tile (row
+        tile fastest), then 0 for the idle records; the same for both dtypes.
+        Host arithmetic only; needs no GPU."""
+        out = (ctypes.c_uint64 * (4 * self.moe_skinny_tiles(slots, len(counts), n)))()
+        rc = self.lib.na_moe_skinny_expected(seed, tokens, slots, len(counts), n, k,
+                                             (ctypes.c_int * len(counts))(*counts), reps, out,
+                                             len(out))
+        self._check(rc, "moe_skinny_expected")
+        return list(out)
+
+    def moe_skinny_run(self, dev: int, x: int, w: int, row_ids: int, offsets: int, tokens: int,
+                       slots: int, experts: int, n: int, k: int, reps: int = 1,
+                       seed: int = DEFAULT_MOE_SKINNY_SWEEP_SEED, dtype: str = "bf16",
+                       c: int = 0) -> tuple:
+        """One launch of the skinny expert GEMM: ``moe_gemm_run``'s operation,
+        tensors and arguments (``c`` 16-byte aligned) in tiles of 16 slots, for
+        1-16 slots per expert. Returns ``(records, ms)``."""
+        return self._sweep_run(
+            "moe_skinny_run", MfmaRecord, 4 * self.moe_skinny_tiles(slots, experts, n),
+            dev, self._matrix_code("mfma", dtype), x, w, row_ids, offsets, c or None, tokens,
+            slots, experts, n, k, reps, seed,
+        )
+
+    def moe_skinny_verify(self, recs, tokens: int, slots: int, n: int, k: int, counts,
+                          reps: int = 1, seed: int = DEFAULT_MOE_SKINNY_SWEEP_SEED,
+                          dtype: str = "bf16") -> tuple:
+        """Compare every record against the host reference of ``moe_gemm_fill``'s
+        tensors: the tiles' checksums, and that exactly the records behind them
+        are idle. Returns ``(rc, MoeSkinnySweepResult)``; rc is
+        ``NA_ERR_VERIFY`` on any bad record, and ``na_last_error`` then names
+        the first by unit, expert, row tile, column tile and wave."""
+        return self._sweep_verify(
+            "moe_skinny_verify", recs,
+            (tokens, slots, len(counts), n, k, (ctypes.c_int * len(counts))(*counts), reps, seed),
+            _MfmaSweepResultC(),
+            lambda res: MoeSkinnySweepResult(MfmaSweepResult._from_c(dtype, res), n, tuple(counts)),
+            MoeSkinnySweepResult,
+        )
+
+    def moe_skinny_sweep(self, dev: int, dtype: str = "bf16", tokens: int = 0, slots: int = 0,
+                         experts: int = 0, n: int = 0, k: int = 0, reps: int = 0,
+                         seed: int = DEFAULT_MOE_SKINNY_SWEEP_SEED) -> MoeSkinnySweepResult:
+        """Allocate and fill the tensors with decode-size counts hashed from the
+        seed (0-16 slots per expert, empty experts and experts of one slot, a
+        few of 17-40, dropped tokens), run the skinny expert GEMM once to warm
+        up and then several times in one timed window, and verify every record
+        bit-exactly. 0 selects the default: ``DEFAULT_MOE_SKINNY_SWEEP_*`` and
+        ``reps`` 1. Wrong records come back in the result (``.ok`` False), not
+        as an exception; operands that do not fit in half of the free device
+        memory raise ``GemmSweepNoRoom``."""
+        res, gbps = _MfmaSweepResultC(), ctypes.c_double(0)
+        rc = self.lib.na_moe_skinny_sweep(dev, self._matrix_code("mfma", dtype), tokens, slots,
+                                          experts, n, k, reps, seed, ctypes.byref(res),
+                                          ctypes.byref(gbps))
+        if rc not in (NA_OK, NA_ERR_VERIFY):
+            err = self._err()
+            cls = GemmSweepNoRoom if "do not fit" in err else NodeAgentError
+            raise cls(f"moe_skinny_sweep({dev}): {err}")
+        return MoeSkinnySweepResult(MfmaSweepResult._from_c(dtype, res),
+                                    n or DEFAULT_MOE_SKINNY_SWEEP_N, (), gbps.value)
+
+    def _run_moe_skinny_sweep(self, g: GPUReport) -> None:
+        try:
+            res = self.moe_skinny_sweep(g.index)
+        except GemmSweepNoRoom as e:
+            # a busy GPU must not get its node replaced for lack of free memory
+            g.moe_skinny_sweep_skipped = str(e)
+            return
+        g.moe_skinny_sweep_gbps = round(res.gbps, 1)
+        g.moe_skinny_sweep_clock_mhz = round(res.sweep.clock_mhz, 1)
+        g.moe_skinny_sweep_units_seen = res.sweep.units_seen
+        g.moe_skinny_sweep_bad_waves = res.sweep.bad_waves
+        if res.gbps < MIN_MOE_SKINNY_SWEEP_GBPS:
+            g.problems.append(
+                f"MoE skinny sweep {g.moe_skinny_sweep_gbps} GB/s below floor "
+                f"{MIN_MOE_SKINNY_SWEEP_GBPS}"
+            )
+        if not res.ok:
+            # the library's message names the expert: only it knows the sweep's counts
+            g.problems.append(f"MoE skinny sweep: {res.describe()}; {self._err()}")
+
     # -- chip-wide MoE routing sweep -------------------------------------------------
 
     def moe_route_fill(self, dev: int, logits: int, y: int, tokens: int, experts: int, top_k: int,
@@ -2692,7 +2865,8 @@ class NodeAgent:
               load_sweep: bool = False, gemm_sweep: bool = False,
               mxgemm_sweep: bool = False, mxquant_sweep: bool = False,
               attn_sweep: bool = False, decode_sweep: bool = False,
-              moe_gemm_sweep: bool = False, moe_route_sweep: bool = False) -> NodeReport:
+              moe_gemm_sweep: bool = False, moe_route_sweep: bool = False,
+              moe_skinny_sweep: bool = False) -> NodeReport:
         """Full health battery. ``memtest_bytes`` > 0 additionally runs the
         HBM data-integrity test on that many bytes per GPU, clamped to 90 %
         of what the device reports free; if nothing can be allocated the
@@ -2802,6 +2976,15 @@ class NodeAgent:
         unit, as is a rate under ``MIN_MOE_ROUTE_SWEEP_MTOKS`` or
         ``MIN_MOE_COMBINE_SWEEP_GBPS``; tensors that do not fit land in
         ``moe_route_sweep_skipped``. False (default) makes no new library
+        call.
+
+        ``moe_skinny_sweep`` additionally runs the chip-wide decode-size MoE
+        expert GEMM sweep on every GPU: the bf16 expert GEMM at 0-40 slots per
+        expert in tiles of 16 slots, 1 GiB of expert weights streamed from HBM
+        straight into the matrix cores. A wrong record is a problem that names
+        its expert, row tile, column tile, wave and unit, as is a rate under
+        ``MIN_MOE_SKINNY_SWEEP_GBPS``; operands that do not fit land in
+        ``moe_skinny_sweep_skipped``. False (default) makes no new library
         call."""
         report = NodeReport()
         report.gpu_count = self.device_count()
@@ -2864,6 +3047,8 @@ class NodeAgent:
                     self._run_moe_gemm_sweep(g)
                 if moe_route_sweep:
                     self._run_moe_route_sweep(g)
+                if moe_skinny_sweep:
+                    self._run_moe_skinny_sweep(g)
             except NodeAgentError as e:
                 g.problems.append(str(e))
             g.healthy = not g.problems
@@ -3089,6 +3274,17 @@ def main(argv=None) -> int:
         "through route + sort and the combine's bytes per second",
     )
     ap.add_argument(
+        "--moe-skinny-sweep",
+        action="store_true",
+        help="also run the chip-wide decode-size MoE expert GEMM sweep on every GPU: the bf16 "
+        "expert GEMM at decode counts (0-16 slots per expert over 128 experts, a few of 17-40) in "
+        "tiles of 16 slots x 256 columns found by each workgroup from the offsets in device "
+        "memory, 1 GiB of expert weights streamed from HBM straight into the matrix cores and "
+        "the gathered rows shared through LDS; every wave's checksum over its 64 columns and the "
+        "tile's valid rows is recomputed on the host and a wrong one attributed to its "
+        "XCC/SE/SH/CU/SIMD, expert, row tile, column tile and wave; reports bytes per second",
+    )
+    ap.add_argument(
         "--patch-node",
         default="",
         metavar="NODE",
@@ -3115,6 +3311,7 @@ def main(argv=None) -> int:
             decode_sweep=args.decode_sweep,
             moe_gemm_sweep=args.moe_gemm_sweep,
             moe_route_sweep=args.moe_route_sweep,
+            moe_skinny_sweep=args.moe_skinny_sweep,
         )
     except NodeAgentError as e:
         print(json.dumps({"healthy": False, "agent_error": str(e)}))

@@ -4019,13 +4019,23 @@ extern "C" int na_decode_sweep(int dev, int batch, int heads, int kv_heads, int 
 // 6 * reps * 1024 < 2^24 allows up to 2730.
 static const int mg_default_reps[2] = {72, 140};
 
+// How a kernel cuts the problem into tiles and a tile over its four waves: the
+// MoE GEMM sweep's and the decode-size sweep's (moeskinnysweep.h).
+struct mg_geometry {
+    int tile_m;         // slots of a row tile
+    int row_groups;     // a tile's rows go to this many waves
+    int col_groups;     // and its 256 columns to this many: wave = wr * col_groups + wc
+    bool rows_fastest;  // tiles of an expert: column tile, then row tile; or row tile first
+};
+static const mg_geometry mg_wide = {MG_TILE_M, 2, 2, false};
+
 static bool mg_shape_ok(long long tokens, long long slots, int experts, long long n, long long k,
-                        int reps, long long bk) {
+                        int reps, long long bk, int tile_m = MG_TILE_M) {
     return tokens >= 1 && tokens <= NA_MOE_MAX_ROWS && slots >= 1 && slots <= NA_MOE_MAX_ROWS &&
            experts >= 1 && experts <= NA_MOE_MAX_EXPERTS && n >= MG_TILE_N &&
            n <= NA_GEMM_MAX_DIM && n % MG_TILE_N == 0 && k >= bk && k % bk == 0 && reps >= 1 &&
            k < NA_GEMM_EXACT && 6 * (long long)reps * k < NA_GEMM_EXACT &&
-           (slots / MG_TILE_M + experts) * (n / MG_TILE_N) <= NA_MFMA_MAX_WORKGROUPS;
+           (slots / tile_m + experts) * (n / MG_TILE_N) <= NA_MFMA_MAX_WORKGROUPS;
 }
 
 #define MG_SHAPE_WORDS                                                                          \
@@ -4037,8 +4047,9 @@ static bool mg_shape_ok(long long tokens, long long slots, int experts, long lon
         MG_TILE_N, NA_GEMM_MAX_DIM, (long long)(n), (long long)(bk), (long long)(k), reps,     \
         NA_MFMA_MAX_WORKGROUPS
 
-static long long mg_bound(long long slots, int experts, long long n) {
-    return (long long)mg_row_tile_bound((uint32_t)slots, (uint32_t)experts) * (n / MG_TILE_N);
+static long long mg_bound(long long slots, int experts, long long n, int tile_m = MG_TILE_M) {
+    return (long long)mg_row_tile_bound((uint32_t)slots, (uint32_t)experts, (uint32_t)tile_m) *
+           (n / MG_TILE_N);
 }
 
 // The first expert whose count is negative or takes the sum past `slots`; -1
@@ -4070,15 +4081,18 @@ extern "C" int na_moe_gemm_tiles(long long slots, int experts, long long n_cols,
 // identity per (row tile, expert): the wave that owns valid slots R and columns
 // S of expert e has reps * sum_k U[k] * V[k] with U[k] = sum_{s in R} p_s
 // X[row_ids[s]][k] and V[k] = sum_{j in S} q_j W[e][j][k]. V is built once per
-// expert and 128-column block, U per half of a row tile: O(slots K + experts N
-// K) hashes. Records of no tile, and sub-tiles with no valid row, stay 0.
+// expert and column group of a wave, U per row group of a row tile: O(slots K +
+// experts N K) hashes. Records of no tile, and sub-tiles with no valid row, stay
+// 0. `geo` says which kernel's tiles, waves and numbering.
 static void mg_expected(uint64_t base, long long tokens, long long slots, int experts, long long n,
-                        long long k, const int* counts, int reps, uint64_t* out) {
+                        long long k, const int* counts, int reps, uint64_t* out,
+                        const mg_geometry& geo = mg_wide) {
     const uint64_t wx = base + (uint64_t)tokens * (uint64_t)k;  // where W starts
     const uint64_t wbase = wx + (uint64_t)experts * (uint64_t)n * (uint64_t)k;
-    const long long nt = n / MG_TILE_N;
-    std::fill(out, out + MS_WAVES_PER_WG * mg_bound(slots, experts, n), (uint64_t)0);
-    std::vector<uint64_t> u((size_t)(2 * k)), v((size_t)(2 * nt * k));
+    const long long nt = n / MG_TILE_N, tile_m = geo.tile_m;
+    const long long wave_m = tile_m / geo.row_groups, wave_n = MG_TILE_N / geo.col_groups;
+    std::fill(out, out + MS_WAVES_PER_WG * mg_bound(slots, experts, n, geo.tile_m), (uint64_t)0);
+    std::vector<uint64_t> u((size_t)(geo.row_groups * k)), v((size_t)(geo.col_groups * nt * k));
     long long row_tile = 0, start = 0;
     for (int e = 0; e < experts; start += counts[e], ++e) {
         if (counts[e] == 0) continue;
@@ -4086,38 +4100,44 @@ static void mg_expected(uint64_t base, long long tokens, long long slots, int ex
         for (long long j = 0; j < n; ++j) {
             const uint64_t q = gs_weight(wbase + (uint64_t)(slots + j));
             const uint64_t at = wx + (uint64_t)(((long long)e * n + j) * k);
-            uint64_t* const row = &v[(size_t)(j / (MG_TILE_N / 2) * k)];
+            uint64_t* const row = &v[(size_t)(j / wave_n * k)];
             for (long long kk = 0; kk < k; ++kk)
                 row[kk] += q * (uint64_t)(int64_t)gs_element(at + (uint64_t)kk, GS_MOD_B);
         }
-        for (long long mi = 0; mi * MG_TILE_M < counts[e]; ++mi, ++row_tile) {
+        const long long mine = (counts[e] + tile_m - 1) / tile_m;
+        for (long long mi = 0; mi < mine; ++mi) {
             std::fill(u.begin(), u.end(), (uint64_t)0);
-            const long long valid = std::min<long long>(MG_TILE_M, counts[e] - mi * MG_TILE_M);
+            const long long valid = std::min<long long>(tile_m, counts[e] - mi * tile_m);
             for (long long r = 0; r < valid; ++r) {
-                const uint64_t s = (uint64_t)(start + mi * MG_TILE_M + r);
+                const uint64_t s = (uint64_t)(start + mi * tile_m + r);
                 const uint64_t p = gs_weight(wbase + s);
                 const uint64_t at = base + (uint64_t)mg_row_id(base, s, (uint32_t)tokens) * (uint64_t)k;
-                uint64_t* const row = &u[(size_t)(r / (MG_TILE_M / 2) * k)];
+                uint64_t* const row = &u[(size_t)(r / wave_m * k)];
                 for (long long kk = 0; kk < k; ++kk)
                     row[kk] += p * (uint64_t)(int64_t)gs_element(at + (uint64_t)kk, GS_MOD_A);
             }
             for (long long w = 0; w < nt * MS_WAVES_PER_WG; ++w) {
-                const long long tj = w / MS_WAVES_PER_WG, wr = w >> 1 & 1, wc = w & 1;
+                const long long tj = w / MS_WAVES_PER_WG, wave = w % MS_WAVES_PER_WG;
+                const long long wr = wave / geo.col_groups, wc = wave % geo.col_groups;
                 const uint64_t* const ur = &u[(size_t)(wr * k)];
-                const uint64_t* const vr = &v[(size_t)((tj * 2 + wc) * k)];
+                const uint64_t* const vr = &v[(size_t)((tj * geo.col_groups + wc) * k)];
                 uint64_t dot = 0;
                 for (long long kk = 0; kk < k; ++kk) dot += ur[kk] * vr[kk];
-                out[row_tile * nt * MS_WAVES_PER_WG + w] = (uint64_t)reps * dot;
+                const long long tile = geo.rows_fastest ? row_tile * nt + tj * mine + mi
+                                                        : (row_tile + mi) * nt + tj;
+                out[tile * MS_WAVES_PER_WG + wave] = (uint64_t)reps * dot;
             }
         }
+        row_tile += mine;
     }
 }
 
 // What the host entry points that take counts check. bk: the dtype's, or the
 // smaller of the two where no dtype is at hand.
 static int mg_host_args(const char* fn, long long tokens, long long slots, int experts,
-                        long long n, long long k, const int* counts, int reps, long long bk) {
-    if (!mg_shape_ok(tokens, slots, experts, n, k, reps, bk) || counts == nullptr)
+                        long long n, long long k, const int* counts, int reps, long long bk,
+                        int tile_m = MG_TILE_M) {
+    if (!mg_shape_ok(tokens, slots, experts, n, k, reps, bk, tile_m) || counts == nullptr)
         return arg_error("%s: need " MG_SHAPE_WORDS " and counts (%p)", fn,
                          MG_SHAPE_ARGS(tokens, slots, experts, n, k, reps, bk),
                          (const void*)counts);
@@ -4342,6 +4362,235 @@ extern "C" int na_moe_gemm_sweep(int dev, int dtype, long long tokens, long long
     if (tflops) *tflops = 2.0 * valid * (double)n_cols * (double)k * reps / (ms * 1e9);
     return na_moe_gemm_verify(recs.data(), (long long)recs.size(), tokens, slots, experts, n_cols,
                               k, counts.data(), reps, seed, res);
+}
+
+// ---------------------------------------------------------------------------
+// Chip-wide decode-size MoE expert GEMM sweep (specification and kernel in
+// moeskinnysweep.h, the kernel compiled in attnsweep.hip)
+// ---------------------------------------------------------------------------
+//
+// The expert GEMM above at decode counts, 1-16 slots per expert: tiles of 16
+// slots x 256 columns, the expert's weights streamed from HBM straight into the
+// MFMAs' A operand, the gathered rows shared through LDS. The problem, the
+// tensors (na_moe_gemm_fill's), the limits, the tile search and the host
+// reference are the MoE GEMM sweep's, with another geometry; the figure is bytes
+// per second.
+
+#include "moeskinnysweep.h"
+
+static const mg_geometry mg_skinny = {SK_TILE_M, 1, 4, true};
+
+// The whole sweep's shape, a decode step: 160 tokens routed top-8 to 128 experts
+// of N = 2048, K = 2048: 1 GiB of bf16 weights, which no cache level holds from
+// one pass to the next (the host reference hashes all of it: about a second).
+#define NA_MOE_SKINNY_DEFAULT_TOKENS 160
+#define NA_MOE_SKINNY_DEFAULT_TOPK 8
+#define NA_MOE_SKINNY_DEFAULT_EXPERTS 128
+#define NA_MOE_SKINNY_DEFAULT_N 2048
+#define NA_MOE_SKINNY_DEFAULT_K 2048
+// Launches in the sweep's timed window, each a whole pass over the weights.
+#define SK_SWEEP_PASSES 8
+
+// Pure host code; no HIP call.
+extern "C" int na_moe_skinny_tiles(long long slots, int experts, long long n_cols,
+                                   long long* bound) {
+    if (!mg_shape_ok(1, slots, experts, n_cols, NA_GEMM_BK_FP8, 1, NA_GEMM_BK_FP8, SK_TILE_M) ||
+        bound == nullptr)
+        return arg_error("na_moe_skinny_tiles: need slots in 1..%d (got %lld), experts in 1..%d "
+                         "(got %d), n_cols a multiple of %d up to %d (got %lld), at most %d "
+                         "workgroups, and a result pointer",
+                         NA_MOE_MAX_ROWS, slots, NA_MOE_MAX_EXPERTS, experts, MG_TILE_N,
+                         NA_GEMM_MAX_DIM, n_cols, NA_MFMA_MAX_WORKGROUPS);
+    *bound = mg_bound(slots, experts, n_cols, SK_TILE_M);
+    return NA_OK;
+}
+
+// Pure host code: all 4 * bound checksums, n_out exactly that.
+extern "C" int na_moe_skinny_expected(unsigned long long seed, long long tokens, long long slots,
+                                      int experts, long long n_cols, long long k,
+                                      const int* counts, int reps, uint64_t* checksums,
+                                      long long n_out) {
+    const int rc = mg_host_args("na_moe_skinny_expected", tokens, slots, experts, n_cols, k, counts,
+                                reps, NA_GEMM_BK_BF16, SK_TILE_M);
+    if (rc != NA_OK) return rc;
+    const long long want = MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols, SK_TILE_M);
+    if (checksums == nullptr || n_out != want)
+        return arg_error("na_moe_skinny_expected: need room for exactly 4 checksums per workgroup "
+                         "(checksums %p, n_out %lld, want %lld)",
+                         (void*)checksums, n_out, want);
+    mg_expected(seed * MS_G, tokens, slots, experts, n_cols, k, counts, reps, checksums, mg_skinny);
+    return NA_OK;
+}
+
+// na_moe_skinny_run's checks and `passes` launches, one behind the other, in one
+// HIP-event window; every pass writes the same records and the same C.
+static int sk_run(const char* fn, int passes, int dev, int dtype, const void* x, const void* w,
+                  const void* row_ids, const void* offsets, void* c, long long tokens,
+                  long long slots, int experts, long long n_cols, long long k, int reps,
+                  unsigned long long seed, na_mfma_record* out, long long n_out, double* ms) {
+    const int rc = mg_dtype_ok(fn, dtype);
+    if (rc != NA_OK) return rc;
+    if (!mg_shape_ok(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype), SK_TILE_M))
+        return arg_error("%s: need " MG_SHAPE_WORDS, fn,
+                         MG_SHAPE_ARGS(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype)));
+    if (x == nullptr || w == nullptr || row_ids == nullptr || offsets == nullptr ||
+        (((uintptr_t)x | (uintptr_t)w | (uintptr_t)c) & 15) != 0 ||
+        (((uintptr_t)row_ids | (uintptr_t)offsets) & 3) != 0)
+        return arg_error("%s: need 16-byte aligned x and w (got %p, %p), 4-byte aligned row_ids and "
+                         "offsets (%p, %p) and c null or 16-byte aligned (%p)",
+                         fn, x, w, row_ids, offsets, c);
+    const long long bound = mg_bound(slots, experts, n_cols, SK_TILE_M);
+    if (out == nullptr || n_out != MS_WAVES_PER_WG * bound)
+        return arg_error("%s: need room for exactly 4 records per workgroup (out %p, n_out %lld, "
+                         "want %lld)",
+                         fn, (void*)out, n_out, MS_WAVES_PER_WG * bound);
+    const uint64_t wbase = seed * MS_G + (uint64_t)tokens * (uint64_t)k +
+                           (uint64_t)experts * (uint64_t)n_cols * (uint64_t)k;
+    return sweep_launch(dev, (size_t)n_out, out, ms, [&](na_mfma_record* records) {
+        for (int pass = 0; pass < passes; ++pass)
+            sk_launch_sweep(dtype, (unsigned)bound, records, static_cast<const mt_vec*>(x),
+                            static_cast<const mt_vec*>(w), static_cast<const int*>(row_ids),
+                            static_cast<const int*>(offsets), static_cast<float*>(c),
+                            (uint32_t)tokens, (uint32_t)slots, (uint32_t)experts,
+                            (uint32_t)(n_cols / MG_TILE_N), (uint32_t)(k / gs_bk(dtype)),
+                            (uint32_t)reps, wbase);
+    });
+}
+
+// One HIP-event timed skinny expert GEMM on caller-owned device tensors: the
+// bound of (slots / 16 + experts) * n_cols / 256 workgroups, each of which finds
+// its tile in `offsets` or reports idle. Arguments, c, safety and `out` as
+// na_moe_gemm_run's, c 16-byte aligned; the checksums match
+// na_moe_skinny_expected on na_moe_gemm_fill's tensors. Argument errors are
+// detected before any HIP call.
+extern "C" int na_moe_skinny_run(int dev, int dtype, const void* x, const void* w,
+                                 const void* row_ids, const void* offsets, void* c,
+                                 long long tokens, long long slots, int experts, long long n_cols,
+                                 long long k, int reps, unsigned long long seed,
+                                 na_mfma_record* out, long long n_out, double* ms) {
+    return sk_run("na_moe_skinny_run", 1, dev, dtype, x, w, row_ids, offsets, c, tokens, slots,
+                  experts, n_cols, k, reps, seed, out, n_out, ms);
+}
+
+// Pure host code. Record i < 4 * tiles is wave i % 4 of a real tile; the records
+// behind them must be idle (na_moe_gemm_verify's rules). Returns NA_ERR_VERIFY on
+// any bad record, with a message that names the first by unit, expert, row tile,
+// column tile and wave; *res is filled either way.
+extern "C" int na_moe_skinny_verify(const na_mfma_record* recs, long long n, long long tokens,
+                                    long long slots, int experts, long long n_cols, long long k,
+                                    const int* counts, int reps, unsigned long long seed,
+                                    na_mfma_sweep_result* res) {
+    const int rc = mg_host_args("na_moe_skinny_verify", tokens, slots, experts, n_cols, k, counts,
+                                reps, NA_GEMM_BK_BF16, SK_TILE_M);
+    if (rc != NA_OK) return rc;
+    const long long records = MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols, SK_TILE_M);
+    if (recs == nullptr || n != records || res == nullptr)
+        return arg_error("na_moe_skinny_verify: need exactly 4 records per workgroup (recs %p, n "
+                         "%lld, want %lld) and a result pointer",
+                         (const void*)recs, n, records);
+    std::vector<uint64_t> want((size_t)n);
+    mg_expected(seed * MS_G, tokens, slots, experts, n_cols, k, counts, reps, want.data(),
+                mg_skinny);
+    ms_tally(recs, n, true, res, [&](long long i) { return want[(size_t)i]; });
+    if (res->bad_waves == 0) return NA_OK;
+    const uint32_t* u = res->first_bad_unit;
+    const long long w = (long long)res->first_bad_wave, nt = n_cols / MG_TILE_N;
+    long long tile = w / MS_WAVES_PER_WG;
+    char what[112];
+    std::snprintf(what, sizeof(what), "a surplus workgroup that must report idle");
+    for (int e = 0; e < experts; ++e) {
+        const long long mine = (counts[e] + SK_TILE_M - 1) / SK_TILE_M;
+        if (tile < mine * nt) {
+            std::snprintf(what, sizeof(what), "expert %d row tile %lld column tile %lld wave %lld",
+                          e, tile % mine, tile / mine, w % MS_WAVES_PER_WG);
+            break;
+        }
+        tile -= mine * nt;
+    }
+    return na_error(NA_ERR_VERIFY,
+                    "moe skinny sweep: %llu of %llu records wrong on %llu CU(s), first record %lld "
+                    "(%s) on xcc%u.se%u.sh%u.cu%u.simd%u",
+                    (unsigned long long)res->bad_waves, (unsigned long long)res->waves,
+                    (unsigned long long)res->bad_units, w, what, u[0], u[1], u[2], u[3], u[4]);
+}
+
+// The whole sweep's counts, a decode step: expert e draws h = mix64(seed G - 2^41
+// - e); h % 16 = 0 is an empty expert, 1 an expert of one slot, 2 an expert of 17
+// + (h >> 8) % 24 slots (a second and third row tile), anything else (h >> 8) %
+// 17 slots, cut where the slots run out. What is left over are dropped tokens.
+static std::vector<int> sk_default_counts(uint64_t base, long long slots, int experts) {
+    std::vector<int> counts((size_t)experts);
+    long long left = slots;
+    for (int e = 0; e < experts; ++e) {
+        const uint64_t h = mt_mix64(base - ((uint64_t)1 << 41) - (uint64_t)e);
+        const long long draw = h % 16 == 0   ? 0
+                               : h % 16 == 1 ? 1
+                               : h % 16 == 2 ? 17 + (long long)((h >> 8) % 24)
+                                             : (long long)((h >> 8) % 17);
+        counts[(size_t)e] = (int)std::min(draw, left);
+        left -= counts[(size_t)e];
+    }
+    return counts;
+}
+
+// Whole sweep on tensors the agent allocates and fills itself: one untimed
+// warm-up launch, then SK_SWEEP_PASSES launches in one timed window, the verify
+// of the last one's records. 0 = default for tokens (160), slots (8 tokens),
+// experts (128), n_cols (2048), k (2048) and reps (1); the counts are
+// sk_default_counts'. *gbps counts, per launch, the bytes of W of the experts
+// that have a slot and the gathered rows of X (both times reps) and the rows of C
+// written, over the window's time. With reps = 1 and weights no cache holds that
+// is an HBM figure. Operands over half of the free device memory, or that cannot
+// be allocated, are NA_ERR_ARG.
+extern "C" int na_moe_skinny_sweep(int dev, int dtype, long long tokens, long long slots,
+                                   int experts, long long n_cols, long long k, int reps,
+                                   unsigned long long seed, na_mfma_sweep_result* res,
+                                   double* gbps) {
+    if ((dtype != MS_BF16 && dtype != MS_FP8) || res == nullptr || tokens < 0 || slots < 0 ||
+        experts < 0 || n_cols < 0 || k < 0 || reps < 0)
+        return arg_error("na_moe_skinny_sweep: need dtype 0 (bf16) or 1 (fp8) (got %d), tokens, "
+                         "slots, experts, n_cols, k and reps >= 0 (got %lld, %lld, %d, %lld, %lld, "
+                         "%d) and a result pointer",
+                         dtype, tokens, slots, experts, n_cols, k, reps);
+    if (tokens == 0) tokens = NA_MOE_SKINNY_DEFAULT_TOKENS;
+    if (slots == 0)
+        slots = std::min<long long>(NA_MOE_SKINNY_DEFAULT_TOPK * tokens, NA_MOE_MAX_ROWS);
+    if (experts == 0) experts = NA_MOE_SKINNY_DEFAULT_EXPERTS;
+    if (n_cols == 0) n_cols = NA_MOE_SKINNY_DEFAULT_N;
+    if (k == 0) k = NA_MOE_SKINNY_DEFAULT_K;
+    if (reps == 0) reps = 1;
+    if (!mg_shape_ok(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype), SK_TILE_M))
+        return arg_error("na_moe_skinny_sweep: need " MG_SHAPE_WORDS,
+                         MG_SHAPE_ARGS(tokens, slots, experts, n_cols, k, reps, gs_bk(dtype)));
+    const std::vector<int> counts = sk_default_counts(seed * MS_G, slots, experts);
+    double valid = 0.0, active = 0.0;
+    for (int count : counts) valid += count, active += count > 0;
+    HIP_CHECK(hipSetDevice(dev));
+    const size_t esize = dtype == MS_FP8 ? 1 : 2;
+    const size_t sizes[5] = {(size_t)(tokens * k) * esize, (size_t)experts * (size_t)(n_cols * k) * esize,
+                             (size_t)slots * sizeof(int), ((size_t)experts + 1) * sizeof(int),
+                             (size_t)(slots * n_cols) * sizeof(float)};
+    dev_buf<unsigned char> bufs[5];
+    int rc = gs_alloc("na_moe_skinny_sweep", bufs, sizes, 5, tokens, (long long)experts * n_cols, k);
+    if (rc != NA_OK) return rc;
+    rc = na_moe_gemm_fill(dev, dtype, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, tokens, slots,
+                          experts, n_cols, k, counts.data(), seed);
+    if (rc != NA_OK) return rc;
+    std::vector<na_mfma_record> recs(
+        (size_t)(MS_WAVES_PER_WG * mg_bound(slots, experts, n_cols, SK_TILE_M)));
+    double ms = 0.0;
+    for (int passes : {1, SK_SWEEP_PASSES}) {  // the warm-up, then the timed window
+        rc = sk_run("na_moe_skinny_sweep", passes, dev, dtype, bufs[0].p, bufs[1].p, bufs[2].p,
+                    bufs[3].p, bufs[4].p, tokens, slots, experts, n_cols, k, reps, seed,
+                    recs.data(), (long long)recs.size(), &ms);
+        if (rc != NA_OK) return rc;
+    }
+    if (gbps) {
+        const double read = (active * (double)n_cols + valid) * (double)k * (double)esize * reps;
+        *gbps = SK_SWEEP_PASSES * (read + valid * (double)n_cols * sizeof(float)) / (ms * 1e6);
+    }
+    return na_moe_skinny_verify(recs.data(), (long long)recs.size(), tokens, slots, experts, n_cols,
+                                k, counts.data(), reps, seed, res);
 }
 
 // ---------------------------------------------------------------------------

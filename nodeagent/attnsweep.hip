@@ -19,11 +19,14 @@
 // The MoE routing sweep's kernels (moeroutesweep.h) as well: its weights and
 // the combine's FMA chain are claimed exact.
 
+// The decode-size MoE expert GEMM sweep's kernel (moeskinnysweep.h) with them.
+
 #define AS_KERNELS
 #include "attnsweep.h"
 #include "decodesweep.h"
 #include "moegemmsweep.h"
 #include "moeroutesweep.h"
+#include "moeskinnysweep.h"
 
 void as_launch_fill(unsigned grid, mt_vec* q, mt_vec* k, mt_vec* v, mt_u64 q_vecs, mt_u64 kv_vecs,
                     mt_u64 n_k, as_layout at) {
@@ -73,6 +76,15 @@ void mg_launch_sweep(int dtype, unsigned grid, na_mfma_record* records, const mt
     (dtype == MS_FP8 ? moe_gemm_kernel<MS_FP8> : moe_gemm_kernel<MS_BF16>)<<<dim3(grid),
                                                                             dim3(MS_BLOCK),
                                                                             MG_LDS_BYTES>>>(
+        records, x, w, row_ids, offsets, c, tokens, slots, experts, nt, ksteps, reps, wbase);
+}
+
+void sk_launch_sweep(int dtype, unsigned grid, na_mfma_record* records, const mt_vec* x,
+                     const mt_vec* w, const int* row_ids, const int* offsets, float* c,
+                     uint32_t tokens, uint32_t slots, uint32_t experts, uint32_t nt,
+                     uint32_t ksteps, uint32_t reps, mt_u64 wbase) {
+    (dtype == MS_FP8 ? moe_skinny_kernel<MS_FP8> : moe_skinny_kernel<MS_BF16>)<<<dim3(grid),
+                                                                                dim3(MS_BLOCK)>>>(
         records, x, w, row_ids, offsets, c, tokens, slots, experts, nt, ksteps, reps, wbase);
 }
 

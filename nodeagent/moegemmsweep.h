@@ -155,9 +155,11 @@ __device__ __host__ inline uint32_t mg_row_id(mt_u64 base, mt_u64 s, uint32_t to
     return (uint32_t)(mt_mix64(base - 1 - s) % tokens);
 }
 
-// The launch and record bound in row tiles: see "Tile list on the device".
-__device__ __host__ inline uint32_t mg_row_tile_bound(uint32_t slots, uint32_t experts) {
-    return slots / MG_TILE_M + experts;
+// The launch and record bound in row tiles of tile_m slots: see "Tile list on
+// the device".
+__device__ __host__ inline uint32_t mg_row_tile_bound(uint32_t slots, uint32_t experts,
+                                                      uint32_t tile_m = MG_TILE_M) {
+    return slots / tile_m + experts;
 }
 
 // The tile block b computes when `tiles` are real (see "Block to tile");
@@ -217,7 +219,7 @@ struct mg_tile {
     uint32_t idle;
     uint32_t expert;
     uint32_t first;   // the slot of the tile's row 0
-    uint32_t valid;   // 1..128 rows of it belong to the expert
+    uint32_t valid;   // 1..TILE_M rows of it belong to the expert
     uint32_t tj;      // column tile
 };
 
@@ -245,7 +247,10 @@ __device__ inline uint32_t mg_scan(uint32_t v, uint32_t* four, uint32_t* total, 
 
 // See "Tile list on the device". words: 16 words of LDS nobody else uses until
 // the next barrier after the call. Every thread of the workgroup calls it and
-// gets the same answer. Three barriers.
+// gets the same answer. Three barriers. TILE_M: the slots of a row tile.
+// ROWS_FASTEST: within an expert the tiles are numbered column tile, then row
+// tile (moeskinnysweep.h); row tile, then column tile, otherwise.
+template <int TILE_M = MG_TILE_M, bool ROWS_FASTEST = false>
 __device__ inline mg_tile mg_find_tile(uint32_t* words, const int* __restrict__ offsets,
                                        uint32_t slots, uint32_t experts, uint32_t nt,
                                        uint32_t block) {
@@ -258,7 +263,7 @@ __device__ inline mg_tile mg_find_tile(uint32_t* words, const int* __restrict__ 
     const uint32_t start =
         mg_scan(lo, words, nullptr, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
     const uint32_t cnt = (hi > start ? hi : start) - start;  // 0 for threads past `experts`
-    const uint32_t mine = (cnt + MG_TILE_M - 1) / MG_TILE_M;
+    const uint32_t mine = (cnt + TILE_M - 1) / TILE_M;
     uint32_t row_tiles;
     const uint32_t upto =
         mg_scan(mine, words + 4, &row_tiles, [](uint32_t a, uint32_t b) { return a + b; });
@@ -266,18 +271,30 @@ __device__ inline mg_tile mg_find_tile(uint32_t* words, const int* __restrict__ 
     t.index = mg_tile_of_block(block, row_tiles * nt);
     t.idle = block >= row_tiles * nt;
     if (t.idle) return t;  // uniform: depends on the block alone
-    const uint32_t rt = t.index / nt;
-    t.tj = t.index % nt;
-    if (upto - mine <= rt && rt < upto) {  // exactly one thread
-        const uint32_t mi = rt - (upto - mine);
-        words[8] = e;
-        words[9] = start + mi * MG_TILE_M;
-        words[10] = min(cnt - mi * MG_TILE_M, (uint32_t)MG_TILE_M);
+    if constexpr (ROWS_FASTEST) {
+        const uint32_t before = (upto - mine) * nt;  // the tiles of the experts below e
+        if (before <= t.index && t.index < upto * nt) {  // exactly one thread; mine >= 1
+            const uint32_t mi = (t.index - before) % mine;
+            words[8] = e;
+            words[9] = start + mi * TILE_M;
+            words[10] = min(cnt - mi * TILE_M, (uint32_t)TILE_M);
+            words[11] = (t.index - before) / mine;
+        }
+    } else {
+        const uint32_t rt = t.index / nt;
+        t.tj = t.index % nt;
+        if (upto - mine <= rt && rt < upto) {  // exactly one thread
+            const uint32_t mi = rt - (upto - mine);
+            words[8] = e;
+            words[9] = start + mi * TILE_M;
+            words[10] = min(cnt - mi * TILE_M, (uint32_t)TILE_M);
+        }
     }
     __syncthreads();
     t.expert = words[8];
     t.first = words[9];
     t.valid = words[10];
+    if constexpr (ROWS_FASTEST) t.tj = words[11];
     return t;
 }
 

@@ -69,6 +69,7 @@
 #define NA_MOE_TILE_N 256        // its N is a multiple of this (K and reps as the GEMM sweep's),
 #define NA_MOE_MAX_EXPERTS 256   // with at most this many experts
 #define NA_MOE_MAX_ROWS (1 << 22)  // and tokens and slots
+#define NA_MOE_SKINNY_TILE_M 16  // slots in a tile of the decode-size MoE expert GEMM sweep
 #define NA_MOE_MAX_TOPK 8        // choices of a token in the MoE routing sweep,
 #define NA_MOE_ROUTE_BLOCK 256   // tokens of a workgroup of its route and sort (4 records),
 #define NA_MOE_COMBINE_WAVE_TOKENS 8  // and of a wave of its combine (1 record)
@@ -96,7 +97,8 @@
 // * batch * kv_heads * splits + b * kv_heads + hk. The MoE grouped GEMM sweep
 // (moegemmsweep.h) leaves it for each wave of each tile, `wave` being 4 * tile
 // + 2 * wr + wc, and with checksum 0 for each wave of the workgroups beyond the
-// last tile. The MoE routing sweep (moeroutesweep.h) leaves it for each wave of
+// last tile; the decode-size MoE expert GEMM sweep (moeskinnysweep.h) the same,
+// `wave` being 4 * tile + wave. The MoE routing sweep (moeroutesweep.h) leaves it for each wave of
 // its route, scatter and combine kernels, numbered one kernel behind the other
 // as its prototypes below say.
 typedef struct {
@@ -467,6 +469,36 @@ int na_moe_gemm_verify(const na_mfma_record* recs, long long n, long long tokens
 int na_moe_gemm_sweep(int dev, int dtype, long long tokens, long long slots, int experts,
                       long long n_cols, long long k, int reps, unsigned long long seed,
                       na_mfma_sweep_result* res, double* tflops);
+
+// chip-wide decode-size MoE expert GEMM sweep, and the skinny expert GEMM it
+// runs as an operation: the problem, the tensors, the dtypes and the limits of
+// na_moe_gemm_* above (na_moe_gemm_fill fills for both; c here 16-byte aligned),
+// for 1-16 slots per expert, where the expert weights stream from HBM straight
+// into the matrix cores. Tiles of 16 slots x 256 columns are found on the
+// device: na_moe_skinny_tiles' `bound` is (slots / 16 + experts) * n_cols / 256
+// workgroups, and a launch leaves 4 * bound records: 4 * tile + w for wave w,
+// which owns columns 64 w .. 64 w + 63 of the tile, tiles numbered by expert,
+// column tile, row tile (row tile fastest), and idle records behind them.
+// Specification in moeskinnysweep.h. 0 = the default for na_moe_skinny_sweep's
+// shape (a decode step: 160 tokens top-8 on 128 experts of n_cols 2048, k 2048,
+// counts of 0-16 and a few of 17-40 hashed from the seed) and reps (1); *gbps
+// counts the bytes of W of the experts that have a slot, the gathered rows of X
+// and the rows of C written, per second, over several launches in one window.
+int na_moe_skinny_tiles(long long slots, int experts, long long n_cols, long long* bound);
+int na_moe_skinny_expected(unsigned long long seed, long long tokens, long long slots, int experts,
+                           long long n_cols, long long k, const int* counts, int reps,
+                           uint64_t* checksums, long long n_out);
+int na_moe_skinny_run(int dev, int dtype, const void* x, const void* w, const void* row_ids,
+                      const void* offsets, void* c, long long tokens, long long slots, int experts,
+                      long long n_cols, long long k, int reps, unsigned long long seed,
+                      na_mfma_record* out, long long n_out, double* ms);
+int na_moe_skinny_verify(const na_mfma_record* recs, long long n, long long tokens,
+                         long long slots, int experts, long long n_cols, long long k,
+                         const int* counts, int reps, unsigned long long seed,
+                         na_mfma_sweep_result* res);
+int na_moe_skinny_sweep(int dev, int dtype, long long tokens, long long slots, int experts,
+                        long long n_cols, long long k, int reps, unsigned long long seed,
+                        na_mfma_sweep_result* res, double* gbps);
 
 // chip-wide MoE routing sweep, and the three operations it runs on caller-owned
 // tensors around the expert GEMM above (specification, operands and checksums
